@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: frames/s of e2e_mask_rcnn_R-50-FPN_1x inference on synthetic
-800x1333 frames (BASELINE.json configs[1]), plus the RoIAlign HBM roofline and
-the reference CPU path timed on the host.
+800x1333 frames (BASELINE.json configs[1]); with --full also the per-stage
+breakdown, the RoIAlign HBM roofline and the other per-kernel rooflines, and the
+reference CPU path timed on the host.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch F]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch F] [--full]
+                  [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+if --dump-outputs is given, and prints the line; everything else is --full's.
 
 One process per GPU (torchrun for N>1, RCCL).  A step = every rank uploads its own
 F u8 frames from pinned host memory (side stream, inside the timed region) and runs
@@ -879,6 +884,50 @@ def timed_region(loop, steps, sync, barrier=None, watchdog=None, clock=time.perf
     return clock() - t0, out
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all arrays together stay below this
+
+
+def step_outputs(out):
+    """What a caller of the timed path receives from one completed step, as host
+    arrays: dets [F,cap,5] and classes [F,cap] with the rows past each frame's
+    count zeroed (a caller reads counts[f] rows; what the kernels leave behind
+    them is not part of the result), counts [F], and the M = sum(counts)
+    class-selected masks."""
+    counts = np.asarray(out["counts_host"], np.int64)
+    arrays = {"counts": counts.astype(np.float32)}
+    for name in ("dets", "classes"):
+        if name in out:
+            a = out[name].detach().cpu().numpy().astype(np.float32)
+            live = np.arange(a.shape[1])[None, :] < counts[:, None]
+            arrays[name] = np.where(live.reshape(live.shape + (1,) * (a.ndim - 2)), a,
+                                    np.float32(0))
+    if "masks" in out:
+        arrays["masks"] = out["masks"][:int(counts.sum())].detach().cpu().numpy().astype(
+            np.float32)
+    return arrays
+
+
+def dump_outputs(arrays, path, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each array as `path`/<name>.npy (float32), all files
+    together within `budget` bytes.  Smallest first, each array may take an equal
+    share of what is left; one over its share is cut to a fixed sample of its
+    flattened elements (sorted indices drawn from seed 0 for that size), so two
+    runs with the same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    left = budget
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    for i, (name, a) in enumerate(todo):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        # the .npy header stays inside the share; a budget too small for it keeps no element
+        share = max(left // (len(todo) - i) - 4096, 0)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        f = os.path.join(path, name + ".npy")
+        np.save(f, a)
+        left -= os.path.getsize(f)
+
+
 def free_port() -> int:
     import socket
     s = socket.socket()
@@ -1005,6 +1054,46 @@ def make_pipeline(cfg, model, F, layout, dev):
     return FramePipeline(model, cfg, batch=F, channels_last=nhwc, device=dev), 800, 1333
 
 
+CALIBRATE_THREADS = 8  # host threads of build_bench_model's calibration pass
+
+
+def build_bench_model(cfg, dev, channels_last):
+    """weights.build_model with the calibration pass (one synthetic frame through
+    the body, weights.calibrate) run on the host.  On the device that pass goes
+    through MIOpen's one-frame NCHW convolutions, whose small-map solvers split K
+    with atomics: the calibrated weights -- the benchmark's inputs -- then differed
+    in the last bits from process to process, and the step's outputs with them
+    (scores by 1e-4).  torch's CPU convolutions give the same weights every run,
+    so two runs with the same arguments compute on identical inputs.  Everything
+    after the calibration (state dict, folding, layout) is build_model's own, on
+    the device."""
+    from vosdetectron_amd import weights
+    device_calibrate = weights.calibrate
+    calls = []
+
+    def host_calibrate(model, frame_u8, device):
+        # a fixed thread count: the CPU reductions split their work by it
+        threads = torch.get_num_threads()
+        torch.set_num_threads(CALIBRATE_THREADS)
+        try:
+            device_calibrate(model.to("cpu"), frame_u8, "cpu")
+        finally:
+            torch.set_num_threads(threads)
+        calls.append(device)
+        return model.to(device)
+
+    # build_model looks `calibrate` up in its module when it runs
+    weights.calibrate = host_calibrate
+    try:
+        built = weights.build_model(cfg, seed=0, device=dev, channels_last=channels_last)
+    finally:
+        weights.calibrate = device_calibrate
+    if len(calls) != 1:  # build_model no longer calibrates through weights.calibrate
+        raise RuntimeError("bench: the calibration pass did not run on the host (%d calls)"
+                           % len(calls))
+    return built
+
+
 def step_calls(pipe, vos):
     """The pipeline calls the timed step makes (bench.main's step()), as
     (callable, args, kwargs): a test binds them against the engines' signatures
@@ -1034,14 +1123,29 @@ def main():
                          "engines, 16 for VOS / C4)")
     ap.add_argument("--config", default="e2e_mask_rcnn_R-50-FPN_1x")
     ap.add_argument("--layout", default="nhwc", choices=["nchw", "nhwc"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does "
+                         "not need: the per-stage breakdown (stages_ms, segm_results), the "
+                         "RoIAlign / NMS / proposal / conv / GEMM / HBM-copy rooflines and the "
+                         "step roofline, the packed all_gather alone, and the reference's CPU "
+                         "baseline.  Off by default: a plain run sets up, warms up, times the "
+                         "steps and prints the line with those fields null or absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned "
+                         "(dets, classes, counts, masks: step_outputs) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all; inputs and weights are seeded, so two "
+                         "runs with the same arguments dump comparable arrays.  With --gpus N "
+                         "> 1 only rank 0's own frames are dumped, not the gathered results")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=16,
                     help="max frames in the CPU-baseline sample (run until 10 s, >= 2 frames)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the roofline measurements")
     ap.add_argument("--no-timers", dest="timers", action="store_false",
-                    help="skip the per-stage breakdown: by default, after the timed steps, "
-                         "min(--steps, 3) more steps run with HIP-event stage timers and "
-                         "stages_ms is reported (not part of the timed region)")
+                    help="with --full: skip the per-stage breakdown (by default --full runs, "
+                         "after the timed steps, min(--steps, 3) more steps with HIP-event "
+                         "stage timers and reports stages_ms; not part of the timed region)")
     ap.add_argument("--resident", action="store_true",
                     help="frames uploaded once before timing (round-1 definition); default: "
                          "every step uploads its u8 frames from pinned host memory inside the "
@@ -1100,11 +1204,10 @@ def main():
 
     from vosdetectron_amd import config as vcfg
     from vosdetectron_amd.runner import FrameUploader, ResultGatherer
-    from vosdetectron_amd.weights import build_model
 
     cfg = vcfg.get(args.config)
     vos = bool(cfg.get("VOS", False))
-    model, sd = build_model(cfg, seed=0, device=dev, channels_last=args.layout == "nhwc")
+    model, sd = build_bench_model(cfg, dev, args.layout == "nhwc")
     F = args.batch or default_frames(cfg)
     n_host = 4  # distinct pinned host batches cycled through
     pipe, fh, fw = make_pipeline(cfg, model, F, args.layout, dev)
@@ -1128,8 +1231,10 @@ def main():
     loop = StepLoop(pipe, uploader, gatherer, vos=vos, seq_len=args.seq_len,
                     resident=resident if args.resident else None)
 
-    # MIOpen's first-shape search (cudnn.benchmark) keeps the first warm-up step
-    # silent for a minute or more: a heartbeat on stderr shows the run is alive.
+    # With the shipped MIOpen Find results (vosdetectron_amd/miopen_db) the first warm-up
+    # step takes seconds; a configuration or library build they do not cover falls back
+    # to MIOpen's first-shape search (cudnn.benchmark), silent for a minute or more: a
+    # heartbeat on stderr shows the run is alive.
     import threading
     warm_done = threading.Event()
 
@@ -1166,8 +1271,10 @@ def main():
         rank_ms = {"min": round(min(per), 3), "max": round(max(per), 3),
                    "spread": round(max(per) / min(per) - 1, 4), "per_rank": [round(v, 3) for v in per]}
         dt = max(float(x.item()) for x in allt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(out), args.dump_outputs)
     gather_share = None
-    if gatherer.collective and not args.share_gpu:
+    if args.full and gatherer.collective and not args.share_gpu:
         # the packed all_gather ALONE (no compute to hide behind), K times: an upper
         # bound on its share of the step, where it overlaps the next step's compute
         if world > 1:
@@ -1194,7 +1301,7 @@ def main():
 
     stages = None
     extra = {}
-    if args.timers and rank == 0:  # local steps only: no collective on one rank
+    if args.full and args.timers and rank == 0:  # local steps only: no collective on one rank
         pipe.enable_timers()
         for i in range(min(args.steps, 3)):
             pipe.run(any_frames)
@@ -1209,7 +1316,7 @@ def main():
             extra["frames_per_s_incl_segm_per_gpu"] = round(1e3 / (step_ms_frame + segm_ms), 2)
 
     roof = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         roof = measure_roialign_roofline(dev)
         if "X-101" in args.config:
             # SURVEY 8(d) config 5 stress: R = 1000 RoIs at P = 14 (282.1 MB per frame)
@@ -1218,7 +1325,7 @@ def main():
             roof["engine_launch"] = measure_pipeline_roialign(pipe, any_frames)
             extra["nms"] = measure_nms(dev)
             extra.update(measure_step_post(pipe, any_frames))
-    if not args.no_roofline and rank == 0 and world == 1:  # N=1 line only (no ranks waiting)
+    if args.full and not args.no_roofline and rank == 0 and world == 1:  # N=1 line only
         extra["hbm_copy"] = measure_hbm_copy(dev)
         if not vos and cfg.FPN.FPN_ON:
             extra["dominant_kernel"] = measure_dominant_conv(
@@ -1235,7 +1342,7 @@ def main():
             (getattr(pipe, "Hp", fh), getattr(pipe, "Wp", fw)),
             wino_flops, wino4_flops, split3_flops, grouped_adj)
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cpu = cpu_baseline(args.config, sd, args.cpu_frames, cfg=cfg)
 
     if rank == 0:
@@ -1247,7 +1354,8 @@ def main():
             "metric": "frames/sec @1333x800 e2e_mask_rcnn_R-50-FPN, 1/2/4/8 MI355X; "
                       "RoIAlign HBM GB/s",
             "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "warmup": args.warmup, "full": bool(args.full),
+            "ms_per_step": round(dt / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32",
             "arith": "fp32 tensors end to end; the 1x1 convs / fc layers with K >= %d and "
                      "the stem's conv1 run on "

@@ -306,6 +306,89 @@ def test_step_loop_gathers_each_step_once():
     assert kinds == ["gather", "wait", "gather", "wait", "gather", "wait"]
 
 
+def test_bench_model_is_calibrated_on_the_host():
+    """bench.build_bench_model: build_model's calibration pass is handed the model on
+    the CPU, device "cpu", at CALIBRATE_THREADS threads, whatever device the model is
+    built for ("meta" stands in for the GPU here) and whatever the caller's thread
+    count; the model goes back to its device, weights.calibrate and the thread count
+    are put back, and a build_model that stops calling weights.calibrate is an error."""
+    import pytest
+    import torch
+    from vosdetectron_amd import config as vcfg
+    from vosdetectron_amd import weights
+    cfg = vcfg.get("e2e_mask_rcnn_R-50-FPN_1x")
+    seen = []
+
+    def stub(model, frame_u8, device):
+        seen.append((str(device), {p.device.type for p in model.parameters()},
+                     torch.get_num_threads(), frame_u8.shape))
+
+    class Model(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.zeros(2))
+            self.moves = []
+
+        def to(self, device):
+            self.moves.append(str(device))
+            return self
+
+    def fake_build(cfg, seed=0, device="cuda", channels_last=False):
+        m = Model()
+        m.to(device)
+        weights.calibrate(m, np.zeros((4, 4, 3), np.uint8), device)
+        return m, {"seed": seed, "channels_last": channels_last}
+
+    cal, build, n = weights.calibrate, weights.build_model, torch.get_num_threads()
+    try:
+        torch.set_num_threads(3)
+        weights.calibrate, weights.build_model = stub, fake_build
+        m, sd = bench.build_bench_model(cfg, "meta", True)
+        assert weights.calibrate is stub and torch.get_num_threads() == 3
+        assert seen == [("cpu", {"cpu"}, bench.CALIBRATE_THREADS, (4, 4, 3))]
+        assert m.moves == ["meta", "cpu", "meta"] and sd == {"seed": 0, "channels_last": True}
+        weights.build_model = lambda cfg, **kw: (Model(), {})  # calibrates some other way
+        with pytest.raises(RuntimeError, match="did not run on the host"):
+            bench.build_bench_model(cfg, "meta", True)
+        assert weights.calibrate is stub
+    finally:
+        weights.calibrate, weights.build_model = cal, build
+        torch.set_num_threads(n)
+
+
+def test_step_outputs_and_dump(tmp_path):
+    """--dump-outputs: the caller-visible arrays of a completed step (rows past a
+    frame's count zeroed, masks cut to sum(counts)) written as float32 .npy, and an
+    array over its share of the byte budget cut to the same seeded sample twice."""
+    import torch
+    dets = torch.arange(2 * 3 * 5, dtype=torch.float32).view(2, 3, 5) + 1
+    dets[1, 2, 0] = float("nan")  # past frame 1's count: never part of the result
+    out = {"dets": dets, "classes": torch.tensor([[7, 8, 9], [4, 5, 6]], dtype=torch.int32),
+           "counts": torch.tensor([3, 1]), "counts_host": [3, 1],
+           "masks": torch.rand(6, 4, 4)}
+    arrays = bench.step_outputs(out)
+    assert sorted(arrays) == ["classes", "counts", "dets", "masks"]
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert np.array_equal(arrays["dets"][0], dets[0].numpy())
+    assert np.array_equal(arrays["dets"][1, 0], dets[1, 0].numpy())
+    assert not arrays["dets"][1, 1:].any() and not arrays["classes"][1, 1:].any()
+    assert arrays["classes"][1, 0] == 4 and arrays["counts"].tolist() == [3.0, 1.0]
+    assert np.array_equal(arrays["masks"], out["masks"][:4].numpy())
+    bench.dump_outputs(arrays, str(tmp_path / "a"))
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), a), k
+    big = {"x": np.random.default_rng(1).random(100000).astype(np.float32), "y": np.ones(3)}
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d), budget=80000)
+    xb, xc = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert xb.dtype == np.float32 and np.array_equal(xb, xc) and 0 < xb.size < big["x"].size
+    assert np.isin(xb, big["x"]).all()
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 80000
+    bench.dump_outputs(big, str(tmp_path / "d"), budget=100)  # no room: empty samples
+    assert np.load(tmp_path / "d" / "x.npy").size == 0
+
+
 def test_step_watchdog_trips_on_a_stalled_iteration():
     """runner.StepWatchdog: iterations within 10x the median pass; one that runs
     past max(10 x median, floor) trips with its index (on_trip instead of the

@@ -15,7 +15,7 @@ import json,sys
 for l in open(sys.argv[1]): d=json.loads(l); print(d['shape'], d['wino4_us'], d['wino4_exec_frac'], d['wino4_rel_err'])" $OUT/ab_acc$acc.jsonl
 done
 for acc in 0 1; do
-VOSDET_WINO4_ACC=$acc timeout -k 10 300 python -u bench.py > $OUT/bench_acc$acc.json 2> $OUT/bench_acc$acc.err || { tail $OUT/bench_acc$acc.err; exit 1; }
+VOSDET_WINO4_ACC=$acc timeout -k 10 300 python -u bench.py --full > $OUT/bench_acc$acc.json 2> $OUT/bench_acc$acc.err || { tail $OUT/bench_acc$acc.err; exit 1; }
 python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).readlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'])" $OUT/bench_acc$acc.json

@@ -21,7 +21,7 @@ for pmc in "$P1" "$P2"; do i=$((i+1))
 VOSDET_WINO4_ACC=1 timeout -s KILL 120 rocprofv3 --pmc $pmc -d $OUT/pmc_acc1/p$i -o run -- python3 tools/bench_wino4.py 32x256x200x336x256 > $OUT/pmc_acc1_p$i.log 2>&1 || { tail -5 $OUT/pmc_acc1_p$i.log; exit 1; }
 done
 python3 tools/rocpd_pmc.py conv3x3_wino4 $OUT/pmc_acc1.json $OUT/pmc_acc1/p1/run_results.db $OUT/pmc_acc1/p2/run_results.db > /dev/null
-VOSDET_WINO4_ACC=1 timeout -k 10 300 python -u bench.py > $OUT/bench_acc1.json 2> $OUT/bench_acc1.err || { tail $OUT/bench_acc1.err; exit 1; }
+VOSDET_WINO4_ACC=1 timeout -k 10 300 python -u bench.py --full > $OUT/bench_acc1.json 2> $OUT/bench_acc1.err || { tail $OUT/bench_acc1.err; exit 1; }
 python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).readlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'])" $OUT/bench_acc1.json

@@ -15,7 +15,7 @@ for l in open(sys.argv[1]): d=json.loads(l); print(d['shape'], d['wino4_us'], d[
 timeout -k 10 200 python -u tools/bench_wino4_mosaic.py > $OUT/mosaic_ab.jsonl 2> $OUT/m.err || { tail $OUT/m.err; exit 1; }
 cat $OUT/mosaic_ab.jsonl
 for m in 0 1; do
-VOSDET_WINO4_MOSAIC=$m timeout -k 10 300 python -u bench.py > $OUT/bench_mos$m.json 2> $OUT/bench_mos$m.err || { tail $OUT/bench_mos$m.err; exit 1; }
+VOSDET_WINO4_MOSAIC=$m timeout -k 10 300 python -u bench.py --full > $OUT/bench_mos$m.json 2> $OUT/bench_mos$m.err || { tail $OUT/bench_mos$m.err; exit 1; }
 python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).readlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'])" $OUT/bench_mos$m.json

@@ -19,7 +19,7 @@ done
 VOSDET_WINO4_IL=1 timeout -k 10 100 python -u tools/bench_wino4_mosaic.py > $OUT/mosaic_il.jsonl 2> $OUT/m.err || { tail $OUT/m.err; exit 1; }
 cat $OUT/mosaic_il.jsonl
 for il in 0 1; do
-VOSDET_WINO4_IL=$il timeout -k 10 300 python -u bench.py > $OUT/bench_il$il.json 2> $OUT/bench_il$il.err || { tail $OUT/bench_il$il.err; exit 1; }
+VOSDET_WINO4_IL=$il timeout -k 10 300 python -u bench.py --full > $OUT/bench_il$il.json 2> $OUT/bench_il$il.err || { tail $OUT/bench_il$il.err; exit 1; }
 python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).readlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'])" $OUT/bench_il$il.json

@@ -16,7 +16,7 @@ import json,sys
 for l in open(sys.argv[1]): d=json.loads(l); print(d['shape'], d['wino4_us'], d['wino4_exec_frac'])" $OUT/ab.jsonl
 timeout -k 10 100 python -u tools/bench_wino4_mosaic.py > $OUT/mosaic.jsonl 2> $OUT/m.err || { tail $OUT/m.err; exit 1; }
 cat $OUT/mosaic.jsonl
-timeout -k 10 300 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).readlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'])" $OUT/bench_default.json

@@ -5,5 +5,5 @@ cd "${GRAFT_REPO_ROOT:-.}"
 OUT=gpurun_out/r05as
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 600 python -u bench.py --gpus 2 --share-gpu --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_share2.json 2> $OUT/bench_share2.err || { tail -20 $OUT/bench_share2.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full --gpus 2 --share-gpu --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_share2.json 2> $OUT/bench_share2.err || { tail -20 $OUT/bench_share2.err; exit 1; }
 tail -c 1500 $OUT/bench_share2.json

@@ -22,7 +22,7 @@ rc=$?
 tail -5 "$OUT/gpu_tests.txt"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc   # 1 = test failures (read them); else stop
 if [ "${BENCH:-0}" = "1" ]; then
-    timeout -k 10 ${BENCH_LIMIT:-400} python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" \
+    timeout -k 10 ${BENCH_LIMIT:-400} python -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" \
         2> "$OUT/bench.err" || exit $?
     tail -c 3000 "$OUT/bench.json"
 fi

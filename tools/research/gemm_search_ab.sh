@@ -4,7 +4,7 @@
 # $O/plans64.txt by a short bench and then benched.  Every GPU step time-limited.
 set -o pipefail
 O=${O:-gpurun_out/gemm_ab}; mkdir -p $O; rm -f $O/plans64.txt
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 timeout -k 10 300 $B > $O/bench_pins16.json 2> $O/bench_pins16.err || exit $?
 VOSDET_GEMM_MAXALGOS=64 VOSDET_GEMM_PLANS=$O/plans64.txt VOSDET_GEMM_PLANS_RECORD=1 \
     timeout -k 10 400 $B --steps 3 --warmup 2 --no-roofline --no-timers > $O/search.json 2> $O/search.err || exit $?
