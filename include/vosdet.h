@@ -544,6 +544,32 @@ int vd_image_resize_to_blob(const uint8_t *frames, int F, int H, int W, const fl
                             double im_scale, int Hr, int Wr, int Hp, int Wp, int nhwc,
                             float *blob, void *stream);
 
+/* Frames of different sizes in one launch: im_list_to_blob (lib/utils/blob.py:
+ * 86-114) over per-frame prep_im_for_blob results, as tools/infer_simple.py and
+ * test_net.py meet them.  Frame f is geom[f].H x geom[f].W x 3 u8 BGR starting
+ * at byte geom[f].offset of `packed` (any offset, no alignment assumed).  It is
+ * prepared exactly as the two entries above prepare it -- LUT copy when
+ * inv_scale == 1, the 2 x 2 area path when inv_scale == 2, INTER_LINEAR
+ * otherwise -- into the top-left Hr x Wr of slice f of the F x 3 x Hp x Wp
+ * (nhwc: F x Hp x Wp x 3) blob; everything else in the slice is written as
+ * zero, so every blob element is written.
+ *
+ * geom is a DEVICE array of F rows and no frame size is a launch argument: a
+ * captured launch (hipGraph) replays with whatever the buffers hold at replay.
+ * inv_scale = 1.0 / im_scale computed on the host in double (cv::resize's
+ * scale); Hr, Wr = rint(H * im_scale), rint(W * im_scale).  The caller keeps
+ * Hr <= Hp, Wr <= Wp and offset + H*W*3 inside `packed`; on the device a row's
+ * extent is clamped to the blob, so a bad row cannot write outside it. */
+typedef struct VdFrameGeom {
+    int64_t offset;   /* bytes into packed */
+    int32_t H, W;     /* the frame */
+    int32_t Hr, Wr;   /* the resized frame */
+    double inv_scale; /* 1 / im_scale */
+} VdFrameGeom;
+int vd_image_resize_to_blob_ragged(const uint8_t *packed, const VdFrameGeom *geom, int F,
+                                   const float *lut, int Hp, int Wp, int nhwc, float *blob,
+                                   void *stream);
+
 /* Convolution epilogue, in place on x (N x C x H x W logical, physical NHWC when
  * nhwc = 1):  x = act((x + bias[c]) + r),  r = 0 (residual_mode 0), residual
  * (+ residual_bias[c]) of the same shape (mode 1), or residual nearest-2x
@@ -700,6 +726,15 @@ int vd_segm_rle(const float *masks, int M, int R, const float *boxes, int box_st
                 void *stream);
 int vd_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, int cap,
                    int32_t *lens, uint8_t *chars, void *stream);
+
+/* vd_segm_rle for detections of frames of different sizes: det_hw is a DEVICE
+ * array [M][2] = (im_h, im_w) of each detection's own frame, replacing the two
+ * scalar arguments; the kernel body, counts, ncounts and the retry contract
+ * are vd_segm_rle's.  A row with im_h < 1, im_w < 1 or im_w > 8192 gets
+ * ncounts[m] = 0 and no counts (a valid plane has at least one run). */
+int vd_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int box_stride,
+                       const int32_t *det_hw, float thresh, uint32_t *counts, int cap,
+                       int32_t *ncounts, void *stream);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,11 @@ class VdRpnLevel(ctypes.Structure):
                 ("W", ctypes.c_int), ("spatial_scale", ctypes.c_float)]
 
 
+class VdFrameGeom(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("Hr", ctypes.c_int32), ("Wr", ctypes.c_int32), ("inv_scale", ctypes.c_double)]
+
+
 # name -> (restype, argtypes)
 _P, _I, _F, _S, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 SIGNATURES = {
@@ -109,6 +114,7 @@ SIGNATURES = {
     "vd_image_to_blob": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "vd_image_resize_to_blob": (_I, [_P, _I, _I, _I, _P, ctypes.c_double, _I, _I, _I, _I, _I,
                                      _P, _P]),
+    "vd_image_resize_to_blob_ragged": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "vd_nchw_to_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "vd_bias_act": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vd_detections_postfilter": (_I, [_P, _P, _P, _I, _I, _F, _I, _P]),
@@ -122,6 +128,7 @@ SIGNATURES = {
     "vd_bias_relu_maxpool": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "vd_rpn_head": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vd_segm_rle": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P, _I, _P, _P]),
+    "vd_segm_rle_ragged": (_I, [_P, _I, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "vd_rle_strings": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     # VOS temporal path
     "vd_flow_align_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),

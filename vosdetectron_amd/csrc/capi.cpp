@@ -467,6 +467,14 @@ int vd_image_resize_to_blob(const uint8_t *frames, int F, int H, int W, const fl
                                  VD_STREAM(stream));
 }
 
+int vd_image_resize_to_blob_ragged(const uint8_t *packed, const VdFrameGeom *geom, int F,
+                                   const float *lut, int Hp, int Wp, int nhwc, float *blob,
+                                   void *stream) {
+    if (!packed || !geom || !lut || !blob || F < 1 || Hp < 1 || Wp < 1) return VD_ERR_ARG;
+    return launch_resize_to_blob_ragged(packed, geom, F, lut, Hp, Wp, nhwc, blob,
+                                        VD_STREAM(stream));
+}
+
 int vd_bias_act(float *x, const float *bias, const float *residual, const float *residual_bias,
                 int N, int C, int H, int W, int nhwc, int residual_mode, int relu, void *stream) {
     if (!x || N < 1 || C < 1 || H < 1 || W < 1 || residual_mode < 0 || residual_mode > 2 ||
@@ -643,6 +651,17 @@ int vd_segm_rle(const float *masks, int M, int R, const float *boxes, int box_st
         return VD_ERR_ARG;
     return launch_segm_rle(masks, M, R, boxes, box_stride, im_h, im_w, thresh, counts, cap,
                            ncounts, VD_STREAM(stream));
+}
+
+int vd_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int box_stride,
+                       const int32_t *det_hw, float thresh, uint32_t *counts, int cap,
+                       int32_t *ncounts, void *stream) {
+    if (M == 0) return VD_OK;
+    if (!masks || !boxes || !det_hw || !counts || !ncounts || M < 0 || R < 1 ||
+        box_stride < 4 || cap < 1)
+        return VD_ERR_ARG;
+    return launch_segm_rle_ragged(masks, M, R, boxes, box_stride, det_hw, thresh, counts, cap,
+                                  ncounts, VD_STREAM(stream));
 }
 
 int vd_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, int cap,

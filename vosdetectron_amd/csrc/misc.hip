@@ -182,7 +182,94 @@ int launch_roi_crop_fwd(const float *in, int B, int C, int H, int W, const float
 }
 
 // ---------------------------------------------------------------- frames
-// One thread per 4 padded pixels of one row; u8 BGR triplets -> LUT floats.
+// The per-pixel bodies below are shared by the single-size kernels (every frame
+// H x W, sizes as kernel arguments) and the ragged kernel (a geometry row per
+// frame, read from device memory).  `frame` points at a frame's first byte.
+
+// One blob pixel: NCHW planes or an NHWC triplet.
+__device__ __forceinline__ void blob_store(float *__restrict__ blob, int f, int y, int x, int Hp,
+                                           int Wp, int nhwc, const float v[3]) {
+    if (nhwc) {
+        float *d = blob + (((int64_t)f * Hp + y) * Wp + x) * 3;
+        d[0] = v[0];
+        d[1] = v[1];
+        d[2] = v[2];
+    } else {
+        const int64_t plane = (int64_t)Hp * Wp;
+        float *d = blob + (int64_t)f * 3 * plane + (int64_t)y * Wp + x;
+        d[0] = v[0];
+        d[plane] = v[1];
+        d[2 * plane] = v[2];
+    }
+}
+
+// Identity scale: u8 BGR triplet -> LUT floats.  px = the pixel's first byte.
+__device__ __forceinline__ void lut_pixel(const float *slut, const uint8_t *px, float v[3]) {
+    v[0] = slut[px[0]];
+    v[1] = slut[256 + px[1]];
+    v[2] = slut[512 + px[2]];
+}
+
+// Both scales exactly 2: OpenCV runs INTER_AREA's fast path instead (mean of
+// each 2 x 2 block, scalar loop order; a partial block at an odd edge
+// averages the taps inside the image)
+__device__ __forceinline__ void area2_pixel(const float *slut, const uint8_t *frame, int H, int W,
+                                            int y, int x, float v[3]) {
+    const int ys = 2 * y, xs = 2 * x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float *L = slut + 256 * c;
+        float sum = 0.f;
+        int cnt = 0;
+        for (int dy = 0; dy < 2 && ys + dy < H; ++dy)
+            for (int dx = 0; dx < 2 && xs + dx < W; ++dx) {
+                sum += L[frame[((int64_t)(ys + dy) * W + xs + dx) * 3 + c]];
+                ++cnt;
+            }
+        v[c] = cnt == 4 ? sum * 0.25f : sum / (float)cnt;
+    }
+}
+
+struct ResizeRow {  // VResizeLinear taps of one output row
+    const uint8_t *row0, *row1;
+    float b0, b1;
+};
+
+__device__ __forceinline__ ResizeRow resize_row(const uint8_t *frame, int H, int W, int y,
+                                                double scale_y) {
+    ResizeRow r;
+    float fy = (float)((y + 0.5) * scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy -= (float)sy;
+    const int r0 = min(max(sy, 0), H - 1);
+    const int r1 = min(max(sy + 1, 0), H - 1);
+    r.row0 = frame + (int64_t)r0 * W * 3;
+    r.row1 = frame + (int64_t)r1 * W * 3;
+    r.b0 = 1.f - fy;
+    r.b1 = fy;
+    return r;
+}
+
+// HResizeLinear on the two tap rows, then VResizeLinear, per channel
+__device__ __forceinline__ void resize_pixel(const float *slut, const ResizeRow &r, int W, int x,
+                                             double scale_x, float v[3]) {
+    float fx = (float)((x + 0.5) * scale_x - 0.5);
+    int sx = (int)floorf(fx);
+    fx -= (float)sx;
+    if (sx < 0) { fx = 0.f; sx = 0; }
+    if (sx >= W - 1) { fx = 0.f; sx = W - 1; }
+    const int sx1 = min(sx + 1, W - 1);
+    const float a0 = 1.f - fx, a1 = fx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float *L = slut + 256 * c;
+        const float d0 = L[r.row0[sx * 3 + c]] * a0 + L[r.row0[sx1 * 3 + c]] * a1;
+        const float d1 = L[r.row1[sx * 3 + c]] * a0 + L[r.row1[sx1 * 3 + c]] * a1;
+        v[c] = d0 * r.b0 + d1 * r.b1;
+    }
+}
+
+// One thread per padded pixel of one row; u8 BGR triplets -> LUT floats.
 __global__ __launch_bounds__(256) void image_to_blob_kernel(const uint8_t *__restrict__ frames,
                                                             int H, int W,
                                                             const float *__restrict__ lut, int Hp,
@@ -194,24 +281,9 @@ __global__ __launch_bounds__(256) void image_to_blob_kernel(const uint8_t *__res
     const int f = blockIdx.z, y = blockIdx.y;
     const uint8_t *src = frames + ((int64_t)f * H + y) * W * 3;
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
-        float b = 0.f, g = 0.f, r = 0.f;
-        if (y < H && x < W) {
-            b = slut[src[x * 3 + 0]];
-            g = slut[256 + src[x * 3 + 1]];
-            r = slut[512 + src[x * 3 + 2]];
-        }
-        if (nhwc) {
-            float *d = blob + (((int64_t)f * Hp + y) * Wp + x) * 3;
-            d[0] = b;
-            d[1] = g;
-            d[2] = r;
-        } else {
-            const int64_t plane = (int64_t)Hp * Wp;
-            float *d = blob + (int64_t)f * 3 * plane + (int64_t)y * Wp + x;
-            d[0] = b;
-            d[plane] = g;
-            d[2 * plane] = r;
-        }
+        float v[3] = {0.f, 0.f, 0.f};
+        if (y < H && x < W) lut_pixel(slut, src + x * 3, v);
+        blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
     }
 }
 
@@ -246,86 +318,21 @@ __global__ __launch_bounds__(256) void resize_to_blob_kernel(
     for (int i = threadIdx.x; i < 768; i += blockDim.x) slut[i] = lut[i];
     __syncthreads();
     const int f = blockIdx.z, y = blockIdx.y;
-    // both scales exactly 2: OpenCV runs INTER_AREA's fast path instead (mean of
-    // each 2 x 2 block, scalar loop order; a partial block at an odd edge
-    // averages the taps inside the image)
-    const bool area2 = scale_x == 2.0 && scale_y == 2.0;
-    if (area2) {
+    const uint8_t *frame = frames + (int64_t)f * H * W * 3;
+    if (scale_x == 2.0 && scale_y == 2.0) {  // area2_pixel
         for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
             float v[3] = {0.f, 0.f, 0.f};
-            if (y < Hr && x < Wr) {
-                const int ys = 2 * y, xs = 2 * x;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float *L = slut + 256 * c;
-                    float sum = 0.f;
-                    int cnt = 0;
-                    for (int dy = 0; dy < 2 && ys + dy < H; ++dy)
-                        for (int dx = 0; dx < 2 && xs + dx < W; ++dx) {
-                            sum += L[frames[(((int64_t)f * H + ys + dy) * W + xs + dx) * 3 + c]];
-                            ++cnt;
-                        }
-                    v[c] = cnt == 4 ? sum * 0.25f : sum / (float)cnt;
-                }
-            }
-            if (nhwc) {
-                float *d = blob + (((int64_t)f * Hp + y) * Wp + x) * 3;
-                d[0] = v[0];
-                d[1] = v[1];
-                d[2] = v[2];
-            } else {
-                const int64_t plane = (int64_t)Hp * Wp;
-                float *d = blob + (int64_t)f * 3 * plane + (int64_t)y * Wp + x;
-                d[0] = v[0];
-                d[plane] = v[1];
-                d[2 * plane] = v[2];
-            }
+            if (y < Hr && x < Wr) area2_pixel(slut, frame, H, W, y, x, v);
+            blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
         }
         return;
     }
-    int r0 = 0, r1 = 0;
-    float b0 = 0.f, b1 = 0.f;
-    if (y < Hr) {
-        float fy = (float)((y + 0.5) * scale_y - 0.5);
-        const int sy = (int)floorf(fy);
-        fy -= (float)sy;
-        r0 = min(max(sy, 0), H - 1);
-        r1 = min(max(sy + 1, 0), H - 1);
-        b0 = 1.f - fy;
-        b1 = fy;
-    }
-    const uint8_t *row0 = frames + ((int64_t)f * H + r0) * W * 3;
-    const uint8_t *row1 = frames + ((int64_t)f * H + r1) * W * 3;
+    ResizeRow r = {frame, frame, 0.f, 0.f};
+    if (y < Hr) r = resize_row(frame, H, W, y, scale_y);
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
         float v[3] = {0.f, 0.f, 0.f};
-        if (y < Hr && x < Wr) {
-            float fx = (float)((x + 0.5) * scale_x - 0.5);
-            int sx = (int)floorf(fx);
-            fx -= (float)sx;
-            if (sx < 0) { fx = 0.f; sx = 0; }
-            if (sx >= W - 1) { fx = 0.f; sx = W - 1; }
-            const int sx1 = min(sx + 1, W - 1);
-            const float a0 = 1.f - fx, a1 = fx;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float *L = slut + 256 * c;
-                const float d0 = L[row0[sx * 3 + c]] * a0 + L[row0[sx1 * 3 + c]] * a1;
-                const float d1 = L[row1[sx * 3 + c]] * a0 + L[row1[sx1 * 3 + c]] * a1;
-                v[c] = d0 * b0 + d1 * b1;
-            }
-        }
-        if (nhwc) {
-            float *d = blob + (((int64_t)f * Hp + y) * Wp + x) * 3;
-            d[0] = v[0];
-            d[1] = v[1];
-            d[2] = v[2];
-        } else {
-            const int64_t plane = (int64_t)Hp * Wp;
-            float *d = blob + (int64_t)f * 3 * plane + (int64_t)y * Wp + x;
-            d[0] = v[0];
-            d[plane] = v[1];
-            d[2 * plane] = v[2];
-        }
+        if (y < Hr && x < Wr) resize_pixel(slut, r, W, x, scale_x, v);
+        blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
     }
 }
 
@@ -338,6 +345,68 @@ int launch_resize_to_blob(const uint8_t *frames, int F, int H, int W, const floa
     dim3 grid((Wp + 255) / 256, Hp, F);
     hipLaunchKernelGGL(resize_to_blob_kernel, grid, dim3(256), 0, s, frames, H, W, lut, scale,
                        scale, Hr, Wr, Hp, Wp, nhwc, blob);
+    return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
+}
+
+// Frames of different sizes in one launch (im_list_to_blob over a list of
+// prep_im_for_blob results, lib/utils/blob.py:86-139): frame f is geom[f].H x
+// geom[f].W x 3 u8 at byte geom[f].offset of `packed` (any offset: byte loads
+// only), prepared exactly as the single-size kernels prepare it -- LUT copy at
+// scale 1, the 2 x 2 area path at exactly 0.5, INTER_LINEAR otherwise -- into the
+// top-left Hr x Wr of its Hp x Wp slice; every other element of the slice is
+// written as zero.  No frame size is a kernel argument: the geometry row is read
+// from device memory (once per block; it is block-uniform), so a captured launch
+// replays with whatever rows the buffer holds then.  The frame's extent is
+// clamped to the blob (and, at scale 1, to the frame), so a bad row cannot
+// write outside the blob.
+__global__ __launch_bounds__(256) void resize_to_blob_ragged_kernel(
+    const uint8_t *__restrict__ packed, const VdFrameGeom *__restrict__ geom,
+    const float *__restrict__ lut, int Hp, int Wp, int nhwc, float *__restrict__ blob) {
+    __shared__ float slut[768];
+    const int f = blockIdx.z, y = blockIdx.y;
+    const VdFrameGeom g = geom[f];  // issued before the LUT staging: the two loads overlap
+    for (int i = threadIdx.x; i < 768; i += blockDim.x) slut[i] = lut[i];
+    __syncthreads();
+    const uint8_t *frame = packed + g.offset;
+    const int H = g.H, W = g.W;
+    const double scale = g.inv_scale;
+    const bool ok = H >= 1 && W >= 1 && scale > 0.0;
+    int Hr = ok ? min(g.Hr, Hp) : 0, Wr = ok ? min(g.Wr, Wp) : 0;
+    if (scale == 1.0) {  // lut_pixel
+        Hr = min(Hr, H);
+        Wr = min(Wr, W);
+        const uint8_t *src = frame + (int64_t)y * W * 3;
+        for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
+            float v[3] = {0.f, 0.f, 0.f};
+            if (y < Hr && x < Wr) lut_pixel(slut, src + x * 3, v);
+            blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
+        }
+        return;
+    }
+    if (scale == 2.0) {  // area2_pixel
+        for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
+            float v[3] = {0.f, 0.f, 0.f};
+            if (y < Hr && x < Wr) area2_pixel(slut, frame, H, W, y, x, v);
+            blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
+        }
+        return;
+    }
+    ResizeRow r = {frame, frame, 0.f, 0.f};
+    if (y < Hr) r = resize_row(frame, H, W, y, scale);
+    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
+        float v[3] = {0.f, 0.f, 0.f};
+        if (y < Hr && x < Wr) resize_pixel(slut, r, W, x, scale, v);
+        blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
+    }
+}
+
+int launch_resize_to_blob_ragged(const uint8_t *packed, const VdFrameGeom *geom, int F,
+                                 const float *lut, int Hp, int Wp, int nhwc, float *blob,
+                                 hipStream_t s) {
+    if (F < 1 || Hp < 1 || Wp < 1 || Hp > 65535 || F > 65535) return VD_ERR_ARG;
+    dim3 grid((Wp + 255) / 256, Hp, F);
+    hipLaunchKernelGGL(resize_to_blob_ragged_kernel, grid, dim3(256), 0, s, packed, geom, lut, Hp,
+                       Wp, nhwc, blob);
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 

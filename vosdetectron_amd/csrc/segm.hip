@@ -290,7 +290,9 @@ __device__ int segm_column_changes(const float *pm, const PasteGeom &g, int x, i
     return cnt;
 }
 
-__global__ __launch_bounds__(256) void segm_rle_kernel(
+// One detection (workgroup) of vd_segm_rle / vd_segm_rle_ragged: H x W is the
+// frame the detection is pasted into.
+__device__ __forceinline__ void segm_rle_body(
     const float *__restrict__ masks, int R, const float *__restrict__ boxes, int box_stride,
     int H, int W, float thresh, uint32_t *__restrict__ counts, int cap,
     int32_t *__restrict__ ncounts) {
@@ -355,6 +357,28 @@ __global__ __launch_bounds__(256) void segm_rle_kernel(
     }
 }
 
+__global__ __launch_bounds__(256) void segm_rle_kernel(
+    const float *__restrict__ masks, int R, const float *__restrict__ boxes, int box_stride,
+    int H, int W, float thresh, uint32_t *__restrict__ counts, int cap,
+    int32_t *__restrict__ ncounts) {
+    segm_rle_body(masks, R, boxes, box_stride, H, W, thresh, counts, cap, ncounts);
+}
+
+// Each detection pasted into its own frame: det_hw[m] = (H, W), block-uniform.
+// A row the body cannot take (the column table holds kSegmMaxW columns, the
+// positions are 32-bit) is flagged with ncounts[m] = 0 and skipped.
+__global__ __launch_bounds__(256) void segm_rle_ragged_kernel(
+    const float *__restrict__ masks, int R, const float *__restrict__ boxes, int box_stride,
+    const int32_t *__restrict__ det_hw, float thresh, uint32_t *__restrict__ counts, int cap,
+    int32_t *__restrict__ ncounts) {
+    const int H = det_hw[2 * (int64_t)blockIdx.x], W = det_hw[2 * (int64_t)blockIdx.x + 1];
+    if (H < 1 || W < 1 || W > kSegmMaxW || (int64_t)H * W > 0xffffffffll) {
+        if (threadIdx.x == 0) ncounts[blockIdx.x] = 0;
+        return;
+    }
+    segm_rle_body(masks, R, boxes, box_stride, H, W, thresh, counts, cap, ncounts);
+}
+
 int launch_segm_rle(const float *masks, int M, int R, const float *boxes, int box_stride,
                     int im_h, int im_w, float thresh, uint32_t *counts, int cap,
                     int32_t *ncounts, hipStream_t s) {
@@ -362,6 +386,16 @@ int launch_segm_rle(const float *masks, int M, int R, const float *boxes, int bo
     if (R < 1 || R > kPasteMaxR || im_w > kSegmMaxW) return VD_ERR_SHAPE;
     hipLaunchKernelGGL(segm_rle_kernel, dim3(M), dim3(256), 0, s, masks, R, boxes, box_stride,
                        im_h, im_w, thresh, counts, cap, ncounts);
+    return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
+}
+
+int launch_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int box_stride,
+                           const int32_t *det_hw, float thresh, uint32_t *counts, int cap,
+                           int32_t *ncounts, hipStream_t s) {
+    if (M == 0) return VD_OK;
+    if (R < 1 || R > kPasteMaxR) return VD_ERR_SHAPE;
+    hipLaunchKernelGGL(segm_rle_ragged_kernel, dim3(M), dim3(256), 0, s, masks, R, boxes,
+                       box_stride, det_hw, thresh, counts, cap, ncounts);
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 

@@ -152,6 +152,9 @@ int launch_image_to_blob(const uint8_t *frames, int F, int H, int W, const float
 int launch_resize_to_blob(const uint8_t *frames, int F, int H, int W, const float *lut,
                           double im_scale, int Hr, int Wr, int Hp, int Wp, int nhwc, float *blob,
                           hipStream_t s);
+int launch_resize_to_blob_ragged(const uint8_t *packed, const VdFrameGeom *geom, int F,
+                                 const float *lut, int Hp, int Wp, int nhwc, float *blob,
+                                 hipStream_t s);
 int launch_bias_act(float *x, const float *bias, const float *z, const float *bias2, int64_t n,
                     int C, int H, int W, int nhwc, int mode, int relu, hipStream_t s);
 int launch_nchw_to_nhwc(const float *in, int B, int C, int H, int W, float *out, hipStream_t s);
@@ -196,6 +199,9 @@ int launch_mask_rle(const uint8_t *planes, int M, int H, int W, uint32_t *counts
 int launch_segm_rle(const float *masks, int M, int R, const float *boxes, int box_stride,
                     int im_h, int im_w, float thresh, uint32_t *counts, int cap,
                     int32_t *ncounts, hipStream_t s);
+int launch_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int box_stride,
+                           const int32_t *det_hw, float thresh, uint32_t *counts, int cap,
+                           int32_t *ncounts, hipStream_t s);
 int launch_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, int cap,
                        int32_t *lens, uint8_t *chars, hipStream_t s);
 

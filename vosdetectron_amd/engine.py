@@ -17,7 +17,9 @@ roi_feature_transform; here nothing inside the step reads the host: the
 detection counts are read once after the step is queued (complete()).  Outputs match the reference's
 `cls_boxes` rows (class-major, proposal order) and the class-selected masks
 that segm_results consumes; `frame_segms` runs segm_results' paste + RLE on
-the device (segm.py).
+the device (segm.py).  RaggedFramePipeline runs frames of different sizes in one
+step (im_list_to_blob, lib/utils/blob.py:86-114): the per-frame geometry lives in a
+RaggedBatch on the device, vd_image_resize_to_blob_ragged builds the blob.
 """
 from __future__ import annotations
 
@@ -65,14 +67,8 @@ class FramePipeline:
     ASYNC = True  # run(sync=False) queues a step with no host read (see run())
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
                  det_cap=256, device="cuda"):
-        self.model = model
-        self.cfg = cfg
-        self.F = batch
+        self._setup(model, cfg, batch, channels_last, det_cap, device)
         self.H, self.W = frame_hw
-        self.device = torch.device(device)
-        self.channels_last = channels_last
-        self.det_cap = det_cap
-        self._nms_options = nms_options(cfg)
         # blob geometry (lib/utils/blob.py:37-161): get_target_scale, cv2.resize
         # to round(H*s) x round(W*s) (done on the device when s != 1), pad to
         # FPN.COARSEST_STRIDE (get_max_shape; the C4 pipeline does not pad)
@@ -82,13 +78,23 @@ class FramePipeline:
         st = cfg.FPN.COARSEST_STRIDE
         self.Hp = int(math.ceil(self.Hr / st) * st)
         self.Wp = int(math.ceil(self.Wr / st) * st)
-        self.lut = torch.from_numpy(ops.pixel_lut(cfg.PIXEL_MEANS)).to(self.device)
         F = batch
         self.im_info = torch.tensor([[self.Hp, self.Wp, scale]] * F, dtype=torch.float32,
                                     device=self.device)
         self.im_scale_t = torch.full((F,), scale, dtype=torch.float32, device=self.device)
         self.im_scale_d = torch.full((F,), scale, dtype=torch.float64, device=self.device)
         self.im_hw = torch.tensor([[self.H, self.W]] * F, dtype=torch.int32, device=self.device)
+
+    def _setup(self, model, cfg, batch, channels_last, det_cap, device):
+        """Everything of the constructor that does not depend on the frame size."""
+        self.model = model
+        self.cfg = cfg
+        self.F = batch
+        self.device = torch.device(device)
+        self.channels_last = channels_last
+        self.det_cap = det_cap
+        self._nms_options = nms_options(cfg)
+        self.lut = torch.from_numpy(ops.pixel_lut(cfg.PIXEL_MEANS)).to(self.device)
         if cfg.FPN.FPN_ON:
             k_min, k_max = cfg.FPN.RPN_MIN_LEVEL, cfg.FPN.RPN_MAX_LEVEL
             self.rpn_levels = list(range(k_min, k_max + 1))
@@ -142,6 +148,12 @@ class FramePipeline:
     def backbone(self, frames):
         return self.model.Conv_Body(self.make_blob(frames))  # [P6, P5, P4, P3, P2]
 
+    def _frame_rows(self, frames):
+        """(F, im_info, im_scale fp32, im_scale fp64, im_hw) of a step's frames: the
+        per-frame rows the proposal, detection and mask-RoI kernels read."""
+        F = frames.shape[0]
+        return F, self.im_info[:F], self.im_scale_t[:F], self.im_scale_d[:F], self.im_hw[:F]
+
     def nhwc_pyramid(self, feats):
         """P2..P5 as B x H x W x C (a free view when the body ran channels_last)."""
         out = []
@@ -174,7 +186,7 @@ class FramePipeline:
 
     def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
         cfg = self.cfg
-        F = frames.shape[0]
+        F, im_info, im_scale_t, im_scale_d, im_hw = self._frame_rows(frames)
         feats = self.backbone(frames)
         self._mark("conv_body")
         # RPN heads on P2..P6 (finest first for the proposal kernel)
@@ -186,7 +198,7 @@ class FramePipeline:
             deltas.append(d.contiguous())
         tst = cfg.TEST
         lrois, lprobs, lcnt = ops.generate_proposals(
-            probs, deltas, self.anchors, self.rpn_scales, self.im_info[:F],
+            probs, deltas, self.anchors, self.rpn_scales, im_info,
             tst.RPN_PRE_NMS_TOP_N, tst.RPN_POST_NMS_TOP_N, tst.RPN_NMS_THRESH, tst.RPN_MIN_SIZE)
         post = int(tst.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
         rois, rlvl, rcnt = ops.collect_distribute(lrois, lprobs, lcnt, post,
@@ -207,7 +219,7 @@ class FramePipeline:
         bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
         dets, dcls, dcnt = ops.box_detections(
             rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
-            self.im_scale_t[:F], self.im_hw[:F], tst.SCORE_THRESH, tst.NMS,
+            im_scale_t, im_hw, tst.SCORE_THRESH, tst.NMS,
             tst.DETECTIONS_PER_IM, cfg.MODEL.BBOX_REG_WEIGHTS, self.det_cap,
             nms_cross_class=tst.NMS_CROSS_CLASS, num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE,
             **self._nms_options)
@@ -223,13 +235,13 @@ class FramePipeline:
         # barring exact score ties at the limit; complete() runs the rest)
         cap = self.mask_rows(F)
         mrois, mlvl, mcls, mtotal = ops.mask_rois(
-            dets, dcls, dcnt, self.im_scale_d[:F], cap, cfg.FPN.ROI_MIN_LEVEL,
+            dets, dcls, dcnt, im_scale_d, cap, cfg.FPN.ROI_MIN_LEVEL,
             cfg.FPN.ROI_MAX_LEVEL)
         out["masks"], out["mask_feat"] = self._mask_batch(pyr, mrois, mlvl, mcls, fast)
         out["mask_rois"], out["mask_total"] = mrois, mtotal
         # the pyramid stays referenced only until complete() (the rare overflow
         # batch reads it); complete() drops it so a kept result does not pin ~1.5 GB
-        out["_pyr"], out["_fast"] = pyr, fast
+        out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
         self._mark("im_detect_mask")
         if sync:
             self.complete(out)
@@ -272,9 +284,8 @@ class FramePipeline:
         M, cap = sum(counts), out["masks"].shape[0]
         if M > cap:  # rows [cap, M): a second, rare batch
             extra = -(-(M - cap) // 64) * 64
-            F = len(counts)
             r2, l2, c2, _ = ops.mask_rois(out["dets"], out["classes"], out["counts"],
-                                          self.im_scale_d[:F], extra, self.cfg.FPN.ROI_MIN_LEVEL,
+                                          out["_im_scale_d"], extra, self.cfg.FPN.ROI_MIN_LEVEL,
                                           self.cfg.FPN.ROI_MAX_LEVEL, row0=cap)
             m2, f2 = self._mask_batch(out["_pyr"], r2, l2, c2, out["_fast"])
             out["masks"] = torch.cat([out["masks"], m2])
@@ -282,6 +293,7 @@ class FramePipeline:
             out["mask_rois"] = torch.cat([out["mask_rois"], r2])
         out.pop("_pyr", None)
         out.pop("_fast", None)
+        out.pop("_im_scale_d", None)
         out["masks"] = out["masks"][:M]
         out["mask_feat"] = out["mask_feat"][:M]
         out["mask_rois"] = out["mask_rois"][:M]
@@ -289,11 +301,174 @@ class FramePipeline:
         return out
 
 
+class RaggedBatch:
+    """One step's inputs of a RaggedFramePipeline at fixed device addresses: the
+    frames packed back to back in `packed` (u8, `capacity` bytes) and, per frame,
+    the VdFrameGeom row (`geom`), `im_info` = (Hp_f, Wp_f, s_f), `im_scale_t`
+    (fp32), `im_scale_d` (fp64) and `im_hw` = (H_f, W_f).  The per-frame rows are
+    views of one device buffer mirrored by one pinned host buffer, so load() is
+    a host fill and two H2D copies on the current stream, with no allocation:
+    a hipGraph captured on this batch replays with whatever load() put there."""
+
+    def __init__(self, F: int, capacity: int, blob_hw, cfg, device):
+        self.F, self.capacity = int(F), int(capacity)
+        self.Hb, self.Wb = blob_hw
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.sizes = None  # [(H, W)] of the loaded frames
+        g = ops.GEOM_DTYPE.itemsize
+        # layout of the row buffer: 8-byte fields first
+        fields = [("geom", torch.uint8, g * F, (F * g,)), ("im_scale_d", torch.float64, 8 * F, (F,)),
+                  ("im_info", torch.float32, 12 * F, (F, 3)),
+                  ("im_scale_t", torch.float32, 4 * F, (F,)),
+                  ("im_hw", torch.int32, 8 * F, (F, 2))]
+        total = sum(n for _, _, n, _ in fields)
+        self._rows = torch.zeros((total,), dtype=torch.uint8, device=self.device)
+        self._h_rows = torch.zeros((total,), dtype=torch.uint8).pin_memory()
+        self._host = {}
+        pos = 0
+        for name, dt, n, shape in fields:
+            setattr(self, name, self._rows[pos:pos + n].view(dt).view(shape))
+            self._host[name] = self._h_rows[pos:pos + n].view(dt).view(shape).numpy()
+            pos += n
+        self._host["geom"] = self._host["geom"].view(ops.GEOM_DTYPE)
+        self.packed = torch.zeros((self.capacity,), dtype=torch.uint8, device=self.device)
+        self._h_packed = torch.zeros((self.capacity,), dtype=torch.uint8).pin_memory()
+        self._h_packed_np = self._h_packed.numpy()
+        self._copied = torch.cuda.Event()  # the staging area is free again after it
+
+    def load(self, frames):
+        """frames: F arrays H_f x W_f x 3 uint8 BGR (numpy, or CPU tensors).  Validates
+        them against the blob bound and the capacity (ValueError before anything is
+        written), fills the pinned staging area and queues the copies."""
+        cfg = self.cfg
+        arrs = [f.numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
+        if len(arrs) != self.F:
+            raise ValueError("the batch holds %d frames, got %d" % (self.F, len(arrs)))
+        for a in arrs:
+            if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+                raise ValueError("a frame must be H x W x 3 uint8, got %s %s" % (a.shape, a.dtype))
+        geo = ops.frame_geometry([a.shape[:2] for a in arrs], cfg.TEST.SCALE, cfg.TEST.MAX_SIZE,
+                                 cfg.FPN.COARSEST_STRIDE)
+        ops.check_geometry(geo, self.Hb, self.Wb, self.capacity)
+        self._copied.synchronize()  # an earlier load's copies have left the staging area
+        h = self._host
+        for f, a in enumerate(arrs):
+            o = geo.offset[f]
+            self._h_packed_np[o:o + a.size] = a.reshape(-1)
+        geo.fill_rows(h["geom"])
+        h["im_info"][:] = geo.im_info()
+        h["im_scale_t"][:] = geo.scale
+        h["im_scale_d"][:] = geo.scale
+        h["im_hw"][:] = geo.sizes
+        self.packed[:geo.nbytes].copy_(self._h_packed[:geo.nbytes], non_blocking=True)
+        self._rows.copy_(self._h_rows, non_blocking=True)
+        self._copied.record()
+        self.sizes = list(geo.sizes)
+        return self
+
+
+class RaggedFramePipeline(FramePipeline):
+    """FramePipeline for frames of different sizes in one step (FPN configs), after
+    the reference's im_list_to_blob (lib/utils/blob.py:86-114): every frame is
+    scaled by its own get_target_scale, placed top-left in one F x 3 x Hb x Wb blob
+    whose bound `blob_hw` is fixed here (a multiple of FPN.COARSEST_STRIDE, at
+    least every frame's own padded size: ops.blob_bound), and zero elsewhere.
+    Per frame, im_info = (Hp_f, Wp_f, s_f) is the row the single-image
+    get_image_blob gives, boxes are divided by s_f and clipped to H_f x W_f, and
+    the mask RoIs are scaled by s_f.
+
+    Not promised: a frame whose own padded size is smaller than the bound does
+    not give the detections it gives when run alone.  Alone, the convolutions
+    pad the feature maps with zeros at the frame's own edge; in the batch they
+    see the bias-driven features of the zero region there (the reference behaves
+    the same whenever it batches).  Feature maps are not masked.
+
+    All per-frame geometry lives in a RaggedBatch on the device and no frame size
+    is a launch argument, so one captured step replays with other sizes."""
+
+    def __init__(self, model, cfg, blob_hw, batch=1, capacity_bytes=None, channels_last=False,
+                 det_cap=256, device="cuda"):
+        if not cfg.FPN.FPN_ON:
+            raise NotImplementedError("RaggedFramePipeline: C4 configs take an unpadded blob; "
+                                      "only the FPN configs are supported")
+        if bool(cfg.get("VOS", False)) or cfg.FPN.USE_GN or cfg.RESNETS.USE_GN:
+            raise NotImplementedError("RaggedFramePipeline: VOS / GroupNorm configs are not "
+                                      "supported (GroupNorm statistics would span the padding)")
+        Hb, Wb = int(blob_hw[0]), int(blob_hw[1])
+        st = int(cfg.FPN.COARSEST_STRIDE)
+        if Hb < st or Wb < st or Hb % st or Wb % st:
+            raise ValueError("blob_hw must be positive multiples of FPN.COARSEST_STRIDE = %d, "
+                             "got %dx%d" % (st, Hb, Wb))
+        self._setup(model, cfg, batch, channels_last, det_cap, device)
+        self.Hp, self.Wp = Hb, Wb
+        # the largest frames that fit the bound are at scale 1
+        self.capacity = int(capacity_bytes) if capacity_bytes else batch * Hb * Wb * 3
+
+    def new_batch(self) -> RaggedBatch:
+        return RaggedBatch(self.F, self.capacity, (self.Hp, self.Wp), self.cfg, self.device)
+
+    def make_blob(self, batch: RaggedBatch):
+        nhwc = self.channels_last
+        blob = ops.image_resize_to_blob_ragged(batch.packed, batch.geom, self.lut, self.Hp,
+                                               self.Wp, nhwc=nhwc)
+        return blob.permute(0, 3, 1, 2) if nhwc else blob  # NCHW view
+
+    def _frame_rows(self, batch: RaggedBatch):
+        return batch.F, batch.im_info, batch.im_scale_t, batch.im_scale_d, batch.im_hw
+
+    @torch.no_grad()
+    def run(self, batch: RaggedBatch, keep_intermediates: bool = False, sync: bool = True):
+        """batch: a loaded RaggedBatch of this pipeline (new_batch().load(frames)).
+        Returns FramePipeline.run's dict plus im_hw, the batch's [F, 2] device rows;
+        sync=False makes no host read and is graph-capturable.  complete() adds
+        frame_hw, the host copy of im_hw that frame_segms sizes each RLE by."""
+        if not isinstance(batch, RaggedBatch) or batch.F != self.F or \
+                (batch.Hb, batch.Wb) != (self.Hp, self.Wp):
+            raise ValueError("run() takes a RaggedBatch made by this pipeline's new_batch()")
+        if batch.sizes is None:
+            raise ValueError("the batch is empty: load() frames first")
+        return super().run(batch, keep_intermediates, sync)
+
+    def _run(self, batch, keep_intermediates=False, sync=True):
+        out = super()._run(batch, keep_intermediates, sync=False)
+        out["im_hw"] = batch.im_hw
+        if sync:
+            self.complete(out)
+        return out
+
+    def complete(self, out: dict) -> dict:
+        first = "counts_host" not in out
+        out = super().complete(out)
+        if first:
+            out["frame_hw"] = [tuple(r) for r in out["im_hw"].cpu().tolist()]
+        return out
+
+
+def _ragged_frame_segms(pipe, out, ks, num_classes):
+    from . import segm
+    boxes = torch.cat([out["dets"][f, :k] for f, k in enumerate(ks)])
+    classes = torch.cat([out["classes"][f, :k] for f, k in enumerate(ks)]).cpu().tolist()
+    sizes = [list(hw) for hw in out["frame_hw"]]
+    det_hw = np.repeat(np.asarray(sizes, np.int32).reshape(-1, 2), ks, axis=0)
+    total = sum(ks)
+    counts, n = ops.segm_rle_counts_ragged(out["masks"][:total], boxes, det_hw,
+                                           pipe.cfg.MRCNN.THRESH_BINARIZE)
+    strings = ops.rle_strings(counts, n)
+    res, start = [], 0
+    for f, k in enumerate(ks):
+        rles = [{"size": sizes[f], "counts": s} for s in strings[start:start + k]]
+        res.append(segm.group_by_class(rles, classes[start:start + k], num_classes))
+        start += k
+    return res
+
+
 def frame_segms(pipe: FramePipeline, out: dict, num_classes: int = 81):
     """segm_results for every frame of a pipeline output: one fused paste + RLE
     launch and one rleToString pass over all frames' detections
     (vosdetectron_amd/segm.py), then the per-frame class grouping.  Returns a
-    list over frames of cls_segms."""
+    list over frames of cls_segms.  A RaggedFramePipeline output (completed) takes
+    vd_segm_rle_ragged: still one launch, each RLE sized by its own frame."""
     from . import segm
     if isinstance(pipe, VOSPipeline) and pipe.heuristics_on():
         raise ValueError("frame_segms skips TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU: use "
@@ -302,6 +477,8 @@ def frame_segms(pipe: FramePipeline, out: dict, num_classes: int = 81):
     total = sum(ks)
     if total == 0:
         return [[[] for _ in range(num_classes)] for _ in ks]
+    if "frame_hw" in out:
+        return _ragged_frame_segms(pipe, out, ks, num_classes)
     boxes = torch.cat([out["dets"][f, :k] for f, k in enumerate(ks)])
     classes = torch.cat([out["classes"][f, :k] for f, k in enumerate(ks)]).cpu().tolist()
     rles = segm.encode_masks(out["masks"][:total], boxes, pipe.H, pipe.W,

@@ -1085,6 +1085,126 @@ def image_resize_to_blob(frames: torch.Tensor, lut: torch.Tensor, im_scale: floa
     return out
 
 
+# ---- frames of different sizes in one blob (vd_image_resize_to_blob_ragged)
+GEOM_DTYPE = np.dtype([("offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("Hr", "<i4"),
+                       ("Wr", "<i4"), ("inv_scale", "<f8")])  # struct VdFrameGeom
+assert GEOM_DTYPE.itemsize == ctypes.sizeof(_lib.VdFrameGeom) == 32
+RAGGED_MAX_WIDTH = 8192  # vd_segm_rle_ragged's column table (kSegmMaxW)
+
+
+class FrameGeometry:
+    """Per-frame geometry of one ragged step, as lists over frames: sizes (H, W),
+    scale (get_target_scale), resized (Hr, Wr), padded (Hp, Wp), offset (bytes into
+    the packed buffer) and nbytes (the packed frames' total)."""
+
+    def __init__(self, sizes, scale, resized, padded, offset, nbytes):
+        self.sizes, self.scale, self.resized, self.padded = sizes, scale, resized, padded
+        self.offset, self.nbytes = offset, nbytes
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def fill_rows(self, rows: np.ndarray) -> np.ndarray:
+        """The VdFrameGeom rows into a GEOM_DTYPE array (inv_scale = 1 / s in double)."""
+        for f, ((H, W), s, (Hr, Wr)) in enumerate(zip(self.sizes, self.scale, self.resized)):
+            rows[f] = (self.offset[f], H, W, Hr, Wr, 1.0 / s)
+        return rows
+
+    def rows(self) -> np.ndarray:
+        return self.fill_rows(np.zeros(len(self), GEOM_DTYPE))
+
+    def im_info(self) -> np.ndarray:
+        """[F, 3] float32 (Hp_f, Wp_f, s_f): each frame's own get_image_blob row."""
+        return np.array([[hp, wp, s] for (hp, wp), s in zip(self.padded, self.scale)],
+                        np.float32).reshape(-1, 3)
+
+
+def frame_geometry(sizes, target_size: float, max_size: float, stride: int) -> FrameGeometry:
+    """get_image_blob's geometry of every (H, W) in `sizes`, in Python doubles exactly
+    as target_scale and resized_hw compute it, with the frames packed back to back."""
+    st = int(stride)
+    sz, scale, resized, padded, offset = [], [], [], [], []
+    pos = 0
+    for H, W in sizes:
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError("frame size must be positive, got %dx%d" % (H, W))
+        s = target_scale(H, W, target_size, max_size)
+        Hr, Wr = resized_hw(H, W, s)
+        sz.append((H, W))
+        scale.append(s)
+        resized.append((Hr, Wr))
+        padded.append((-(-Hr // st) * st, -(-Wr // st) * st))
+        offset.append(pos)
+        pos += H * W * 3
+    return FrameGeometry(sz, scale, resized, padded, offset, pos)
+
+
+def blob_bound(sizes, cfg):
+    """The smallest blob (Hb, Wb) that holds every frame of `sizes` under cfg's
+    TEST.SCALE / TEST.MAX_SIZE / FPN.COARSEST_STRIDE: the maximum of the frames' own
+    padded sizes, as im_list_to_blob's get_max_shape takes it."""
+    geo = frame_geometry(sizes, cfg.TEST.SCALE, cfg.TEST.MAX_SIZE, cfg.FPN.COARSEST_STRIDE)
+    if not len(geo):
+        raise ValueError("blob_bound needs at least one frame size")
+    return max(hp for hp, _ in geo.padded), max(wp for _, wp in geo.padded)
+
+
+def check_geometry(geo: FrameGeometry, Hp: int, Wp: int, capacity: Optional[int] = None):
+    """Host-side validation of a ragged step (the sizes are known here, the kernel
+    only clamps): every resized frame inside the Hp x Wp bound, no frame wider than
+    the ragged RLE kernel takes, the packed frames inside `capacity` bytes."""
+    if len(geo) < 1:
+        raise ValueError("a ragged step needs at least one frame")
+    for f, ((H, W), (Hr, Wr)) in enumerate(zip(geo.sizes, geo.resized)):
+        if Hr > Hp or Wr > Wp:
+            raise ValueError("frame %d (%dx%d, resized %dx%d) is larger than the blob bound "
+                             "%dx%d" % (f, H, W, Hr, Wr, Hp, Wp))
+        if Hr < 1 or Wr < 1:
+            raise ValueError("frame %d (%dx%d) resizes to nothing (%dx%d)" % (f, H, W, Hr, Wr))
+        if W > RAGGED_MAX_WIDTH:
+            raise ValueError("frame %d is %d wide; the ragged path takes widths up to %d"
+                             % (f, W, RAGGED_MAX_WIDTH))
+    if capacity is not None and geo.nbytes > capacity:
+        raise ValueError("the step's frames take %d bytes, the packed buffer holds %d"
+                         % (geo.nbytes, capacity))
+
+
+def image_resize_to_blob_ragged(packed: torch.Tensor, geom, lut: torch.Tensor, Hp: int, Wp: int,
+                                nhwc: bool = False, out: Optional[torch.Tensor] = None):
+    """get_image_blob of F frames of different sizes into one F x 3 x Hp x Wp (nhwc:
+    F x Hp x Wp x 3) blob, each frame top-left and zero elsewhere
+    (vd_image_resize_to_blob_ragged).  packed: 1-D uint8 device tensor, the frames
+    back to back.  geom: a FrameGeometry (validated here against the bound and
+    packed's size, its rows uploaded), or a device uint8 tensor of F VdFrameGeom
+    rows whose owner validated them (engine.RaggedBatch.load) -- then nothing here
+    reads or writes host memory, so the call can be captured."""
+    pk = _need(packed, "packed", torch.uint8)
+    lt = _need(lut, "lut")
+    Hp, Wp = int(Hp), int(Wp)
+    if Hp < 1 or Wp < 1:
+        raise ValueError("blob bound must be positive, got %dx%d" % (Hp, Wp))
+    if isinstance(geom, FrameGeometry):
+        check_geometry(geom, Hp, Wp, pk.numel())
+        rows = torch.from_numpy(geom.rows().view(np.uint8)).to(pk.device)
+    else:
+        rows = _need(geom, "geom", torch.uint8)
+        if rows.numel() < GEOM_DTYPE.itemsize or rows.numel() % GEOM_DTYPE.itemsize:
+            raise ValueError("geom must hold whole VdFrameGeom rows (%d bytes each), got %d "
+                             "bytes" % (GEOM_DTYPE.itemsize, rows.numel()))
+    F = rows.numel() // GEOM_DTYPE.itemsize
+    shape = (F, Hp, Wp, 3) if nhwc else (F, 3, Hp, Wp)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=pk.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda \
+            or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 device tensor of shape %s" % (shape,))
+    check(lib().vd_image_resize_to_blob_ragged(pk.data_ptr(), rows.data_ptr(), F, lt.data_ptr(),
+                                               Hp, Wp, int(nhwc), out.data_ptr(), _stream()),
+          "vd_image_resize_to_blob_ragged")
+    return out
+
+
 # --------------------------------------------------------------------------- #
 # Proposals, collect/distribute, detections                                    #
 # --------------------------------------------------------------------------- #
@@ -1426,6 +1546,42 @@ def segm_rle_counts(masks: torch.Tensor, boxes: torch.Tensor, im_h: int, im_w: i
         if st == VD_ERR_SHAPE:
             return mask_rle_counts(paste_masks(m, b, im_h, im_w, thresh))
         check(st, "vd_segm_rle")
+        need = int((-n).max().item()) if M else 0
+        if need <= cap:
+            return counts, n
+        cap = need
+
+
+def segm_rle_counts_ragged(masks: torch.Tensor, boxes: torch.Tensor, det_hw, thresh: float = 0.5,
+                           cap: Optional[int] = None):
+    """segm_rle_counts for detections of frames of different sizes in one launch
+    (vd_segm_rle_ragged): det_hw [M, 2] = (im_h, im_w) of each detection's own
+    frame, as a host array or a tensor (its values are read on the host: they are
+    validated here, the kernel has no planes fallback for wide frames).  Returns
+    the same (counts, n) as segm_rle_counts called per frame, rows in order."""
+    m = _need(masks, "masks")
+    b = _need(boxes, "boxes")
+    M, R = m.shape[0], m.shape[-1]
+    if b.shape[0] != M or b.dim() != 2 or b.shape[1] < 4:
+        raise ValueError("boxes must be M x >=4, got %s" % (tuple(b.shape),))
+    hw = det_hw.detach().cpu().numpy() if isinstance(det_hw, torch.Tensor) else det_hw
+    hw = np.ascontiguousarray(np.asarray(hw).reshape(-1, 2), dtype=np.int32)
+    if hw.shape[0] != M:
+        raise ValueError("det_hw must be M x 2 = %d x 2, got %s" % (M, hw.shape))
+    if M and (hw.min() < 1 or hw[:, 1].max() > RAGGED_MAX_WIDTH):
+        raise ValueError("det_hw rows must be positive with widths up to %d, got heights "
+                         "%d..%d, widths %d..%d" % (RAGGED_MAX_WIDTH, hw[:, 0].min(),
+                                                    hw[:, 0].max(), hw[:, 1].min(),
+                                                    hw[:, 1].max()))
+    hw_t = torch.from_numpy(hw).to(m.device)
+    cap = int(cap or (4 * (int(hw[:, 1].max()) if M else 1) + 2))
+    while True:
+        counts = torch.empty((M, cap), dtype=torch.int32, device=m.device)
+        n = torch.empty((M,), dtype=torch.int32, device=m.device)
+        check(lib().vd_segm_rle_ragged(m.data_ptr(), M, R, b.data_ptr(), b.shape[1],
+                                       hw_t.data_ptr(), float(np.float32(thresh)),
+                                       counts.data_ptr(), cap, n.data_ptr(), _stream()),
+              "vd_segm_rle_ragged")
         need = int((-n).max().item()) if M else 0
         if need <= cap:
             return counts, n
