@@ -736,6 +736,27 @@ int vd_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int
                        const int32_t *det_hw, float thresh, uint32_t *counts, int cap,
                        int32_t *ncounts, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * keypoint_results' heatmap decode (lib/utils/keypoints.py:103-157
+ * heatmaps_to_keypoints with scores_to_probs :214-222; called from
+ * lib/core/test.py:858-874) on the device.
+ *
+ * vd_heatmaps_to_keypoints: maps R x K x M x M fp32 logits (M <= 64, K <= 32),
+ * boxes R rows of box_stride fp32 (x1, y1, x2, y2 in image coordinates first;
+ * box_stride >= 4, so a detection array is read in place), min_size =
+ * KRCNN.INFERENCE_MIN_SIZE -> out R x 4 x K fp32, rows (x, y, logit, prob): the
+ * reference's xy_preds.  Per RoI: w = max(x2 - x1, 1), Wm = int(ceil(w)) raised
+ * to min_size when min_size > 0 (h, Hm likewise; Wm, Hm <= 8192); each map is
+ * resized to Hm x Wm by cv2.resize INTER_CUBIC on float32 (restated, rows first:
+ * csrc/keypoints.hip) without being written anywhere; per keypoint the first
+ * row-major argmax (xi, yi) gives x = (xi + 0.5) * (w / Wm) + x1 in float64 with
+ * the float32 quotient, y likewise, logit = the value there and
+ * prob = 1 / sum(exp(v - max)) over the resized map.  x, y and logit are
+ * bit-identical for equal inputs; prob carries expf's last-place error.
+ * R == 0 launches nothing. */
+int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
+                             int box_stride, int min_size, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

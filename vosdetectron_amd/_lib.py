@@ -130,6 +130,8 @@ SIGNATURES = {
     "vd_segm_rle": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P, _I, _P, _P]),
     "vd_segm_rle_ragged": (_I, [_P, _I, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "vd_rle_strings": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    # keypoint_results (heatmap decode)
+    "vd_heatmaps_to_keypoints": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     # VOS temporal path
     "vd_flow_align_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_flow_align_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -62,6 +62,13 @@ def default_cfg() -> AttrDict:
             ROI_XFORM_METHOD="RoIAlign", ROI_XFORM_RESOLUTION=7, ROI_XFORM_SAMPLING_RATIO=0,
             DIM_REDUCED=256, DILATION=2, UPSAMPLE_RATIO=1, USE_FC_OUTPUT=False,
             CLS_SPECIFIC_MASK=True, CONV_INIT="GaussianFill", THRESH_BINARIZE=0.5),
+        KRCNN=_d(  # config.py:783-855
+            ROI_KEYPOINTS_HEAD="", HEATMAP_SIZE=-1, UP_SCALE=-1, USE_DECONV=False,
+            DECONV_DIM=256, USE_DECONV_OUTPUT=False, DILATION=1, DECONV_KERNEL=4,
+            NUM_KEYPOINTS=-1, NUM_STACKED_CONVS=8, CONV_HEAD_DIM=256, CONV_HEAD_KERNEL=3,
+            CONV_INIT="GaussianFill", NMS_OKS=False, KEYPOINT_CONFIDENCE="bbox",
+            ROI_XFORM_METHOD="RoIAlign", ROI_XFORM_RESOLUTION=7, ROI_XFORM_SAMPLING_RATIO=0,
+            INFERENCE_MIN_SIZE=0),
         GROUP_NORM=_d(DIM_PER_GP=-1, NUM_GROUPS=32, EPSILON=1e-5),  # config.py:983-989
         CONVGRU=_d(  # config.py:908-921
             HIDDEN_STATE_CHANNELS=(256, 256, 256, 256, 256), KERNEL_SIZE=3, STRIDE=1,
@@ -113,6 +120,27 @@ def _merge(a, b):
             b[k] = v
 
 
+def _merge_yaml(y, cfg):
+    """_merge of a reference YAML.  MODEL.MASK_ON defaults to True here (the mask
+    family) and to False in the reference (config.py:432), which its keypoint YAMLs
+    rely on: a YAML that switches KEYPOINTS_ON on and does not mention MASK_ON gets
+    the reference's default."""
+    _merge(y, cfg)
+    m = y.get("MODEL") or {}
+    if _decode(m.get("KEYPOINTS_ON", False)) is True and "MASK_ON" not in m:
+        cfg["MODEL"]["MASK_ON"] = False
+
+
+KEYPOINT_HEAD = "keypoint_rcnn_heads.roi_pose_head_v1convX"
+
+
+class _WithCfg:
+    """An UNSUPPORTED predicate that also reads other keys: called as fn(value, cfg)."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+
 # Inference options of the reference that change detections and are not built
 # here: (dotted key, "enabled" predicate, where the reference implements it).
 UNSUPPORTED = (
@@ -127,7 +155,16 @@ UNSUPPORTED = (
     ("TEST.MASK_AUG.ENABLED", bool, "mask test-time augmentation, lib/core/test.py:405-480"),
     ("TEST.KPS_AUG.ENABLED", bool, "keypoint test-time augmentation (keypoint heads out of scope)"),
     ("MODEL.USE_DELTA_FLOW", bool, "delta-flow VOS head, lib_vos/vos_modeling/vos_model_builder.py"),
-    ("MODEL.KEYPOINTS_ON", bool, "keypoint heads (out of scope)"),
+    # Keypoint R-CNN is built for the FPN family with the v1convX head and the
+    # plain per-box decode (engine.KeypointFramePipeline)
+    ("KRCNN.NMS_OKS", bool, "OKS NMS of keypoint_results, lib/core/test.py:864-870"),
+    ("KRCNN.ROI_KEYPOINTS_HEAD", _WithCfg(lambda v, c: bool(c.MODEL.KEYPOINTS_ON) and v != KEYPOINT_HEAD),
+     "keypoint head other than %s" % KEYPOINT_HEAD),
+    ("MODEL.KEYPOINTS_ON", _WithCfg(lambda v, c: bool(v) and bool(c.MODEL.MASK_ON)),
+     "MODEL.KEYPOINTS_ON together with MODEL.MASK_ON (one RoI head family per model)"),
+    ("MODEL.KEYPOINTS_ON", _WithCfg(lambda v, c: bool(v) and (not c.FPN.FPN_ON
+                                                              or bool(c.get("VOS", False)))),
+     "MODEL.KEYPOINTS_ON with a C4 (FPN.FPN_ON False) or VOS model"),
 )
 
 
@@ -145,7 +182,7 @@ def check_supported(cfg) -> None:
             v = _get(cfg, key)
         except (KeyError, TypeError):
             continue
-        if enabled(v):
+        if enabled.fn(v, cfg) if isinstance(enabled, _WithCfg) else enabled(v):
             bad.append("%s=%r (%s)" % (key, v, where))
     if bad:
         raise NotImplementedError("inference options not implemented by vosdetectron_amd: "
@@ -158,7 +195,7 @@ def load_cfg(path: str | None = None, overrides: dict | None = None) -> AttrDict
     cfg = default_cfg()
     if path:
         with open(path) as f:
-            _merge(yaml.safe_load(f) or {}, cfg)
+            _merge_yaml(yaml.safe_load(f) or {}, cfg)
     for key, val in (overrides or {}).items():
         d = cfg
         parts = key.split(".")
@@ -220,6 +257,27 @@ def e2e_mask_rcnn_X_101_32x8d_FPN_1x() -> AttrDict:
     return cfg
 
 
+def e2e_keypoint_rcnn_R_50_FPN_1x() -> AttrDict:
+    """configs/baselines/e2e_keypoint_rcnn_R-50-FPN_1x.yaml: the R-50-FPN body, RPN
+    and box head of the mask config, MASK_ON off (the reference's default), the
+    v1convX pose head (8 x 512-channel 3x3 convs on 14x14 RoIAlign) and the deconv
+    output + 2x bilinear upsample to 56x56 heatmaps of 17 keypoints."""
+    return load_cfg(overrides={
+        "FPN.FPN_ON": True, "FPN.MULTILEVEL_ROIS": True, "FPN.MULTILEVEL_RPN": True,
+        "MODEL.CONV_BODY": "FPN.fpn_ResNet50_conv5_body", "MODEL.FASTER_RCNN": True,
+        "MODEL.MASK_ON": False, "MODEL.KEYPOINTS_ON": True,
+        "FAST_RCNN.ROI_BOX_HEAD": "fast_rcnn_heads.roi_2mlp_head",
+        "FAST_RCNN.ROI_XFORM_METHOD": "RoIAlign", "FAST_RCNN.ROI_XFORM_RESOLUTION": 7,
+        "FAST_RCNN.ROI_XFORM_SAMPLING_RATIO": 2,
+        "KRCNN.ROI_KEYPOINTS_HEAD": KEYPOINT_HEAD, "KRCNN.NUM_STACKED_CONVS": 8,
+        "KRCNN.NUM_KEYPOINTS": 17, "KRCNN.USE_DECONV_OUTPUT": True,
+        "KRCNN.CONV_INIT": "MSRAFill", "KRCNN.CONV_HEAD_DIM": 512, "KRCNN.UP_SCALE": 2,
+        "KRCNN.HEATMAP_SIZE": 56, "KRCNN.ROI_XFORM_METHOD": "RoIAlign",
+        "KRCNN.ROI_XFORM_RESOLUTION": 14, "KRCNN.ROI_XFORM_SAMPLING_RATIO": 2,
+        "KRCNN.KEYPOINT_CONFIDENCE": "bbox", "TEST.SCALE": 800, "TEST.MAX_SIZE": 1333,
+        "TEST.NMS": 0.5, "TEST.RPN_PRE_NMS_TOP_N": 1000, "TEST.RPN_POST_NMS_TOP_N": 1000})
+
+
 def vos_R_101_FPN_3x_gn_static_davis() -> AttrDict:
     """lib_vos/tools/R-101-FPN_3x_gn_static_davis.yaml, with the inference-time
     rewrite of lib_vos/tools/infer_davis_sequential.py:104-113 (IDENTITY_TRAINING
@@ -262,6 +320,7 @@ CONFIGS = {
     "e2e_mask_rcnn_R-50-FPN_1x": e2e_mask_rcnn_R_50_FPN_1x,
     "e2e_mask_rcnn_R-101-FPN_2x": e2e_mask_rcnn_R_101_FPN_2x,
     "e2e_mask_rcnn_X-101-32x8d-FPN_1x": e2e_mask_rcnn_X_101_32x8d_FPN_1x,
+    "e2e_keypoint_rcnn_R-50-FPN_1x": e2e_keypoint_rcnn_R_50_FPN_1x,
     "vos_R-101-FPN_3x_gn_static_davis": vos_R_101_FPN_3x_gn_static_davis,
     "vos_R-101-FPN_3x_gn_dynamic_davis": vos_R_101_FPN_3x_gn_dynamic_davis,
 }
@@ -282,7 +341,7 @@ def merge_cfg_from_file(path: str) -> None:
     An ``UNSUPPORTED`` option raises and leaves the global cfg unchanged."""
     with open(path) as f:
         new = copy.deepcopy(cfg)
-        _merge(yaml.safe_load(f) or {}, new)
+        _merge_yaml(yaml.safe_load(f) or {}, new)
     check_supported(new)
     cfg.clear()
     cfg.update(new)

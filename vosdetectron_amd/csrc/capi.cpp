@@ -671,6 +671,16 @@ int vd_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, int ca
     return launch_rle_strings(counts, ncounts, M, cap, lens, chars, VD_STREAM(stream));
 }
 
+int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
+                             int box_stride, int min_size, float *out, void *stream) {
+    if (R == 0) return VD_OK;
+    if (!maps || !boxes || !out || R < 0 || K < 1 || K > 32 || M < 1 || M > 64 ||
+        box_stride < 4 || min_size < 0)
+        return VD_ERR_ARG;
+    return launch_heatmaps_to_keypoints(maps, R, K, M, boxes, box_stride, min_size, out,
+                                        VD_STREAM(stream));
+}
+
 int vd_bias_relu_maxpool(const float *x, const float *bias, int N, int C, int H, int W,
                          float *out, void *stream) {
     if (!x || !bias || !out || N < 0 || C < 0 || H < 0 || W < 0) return VD_ERR_ARG;

@@ -20,6 +20,9 @@ that segm_results consumes; `frame_segms` runs segm_results' paste + RLE on
 the device (segm.py).  RaggedFramePipeline runs frames of different sizes in one
 step (im_list_to_blob, lib/utils/blob.py:86-114): the per-frame geometry lives in a
 RaggedBatch on the device, vd_image_resize_to_blob_ragged builds the blob.
+KeypointFramePipeline runs the Keypoint R-CNN configs: after misc_bbox, the pose head
+and vd_heatmaps_to_keypoints (im_detect_keypoints + keypoint_results, test.py:97-107)
+take the mask stage's place; frame_keypoints groups the result as cls_keyps.
 """
 from __future__ import annotations
 
@@ -87,6 +90,15 @@ class FramePipeline:
 
     def _setup(self, model, cfg, batch, channels_last, det_cap, device):
         """Everything of the constructor that does not depend on the frame size."""
+        if cfg.MODEL.KEYPOINTS_ON and not isinstance(self, KeypointFramePipeline):
+            raise NotImplementedError(
+                "%s: MODEL.KEYPOINTS_ON configs run on KeypointFramePipeline (FPN, frames of "
+                "one size); ragged, C4 and VOS keypoint steps are not built"
+                % type(self).__name__)
+        if not cfg.MODEL.KEYPOINTS_ON and not hasattr(model, "Mask_Head"):
+            raise NotImplementedError(
+                "%s: the model has no Mask_Head (MODEL.MASK_ON False); a box-only step is "
+                "not built" % type(self).__name__)
         self.model = model
         self.cfg = cfg
         self.F = batch
@@ -229,6 +241,15 @@ class FramePipeline:
                "cls_prob": cls_prob, "bbox_pred": bbox_pred}
         if keep_intermediates:  # for stage-wise parity tests
             out.update(feats=feats, rpn_probs=probs, rpn_deltas=deltas, pyramid=pyr)
+        self._roi_heads(out, F, pyr, fast, im_scale_d, keep_intermediates)
+        if sync:
+            self.complete(out)
+        return out
+
+    def _roi_heads(self, out, F, pyr, fast, im_scale_d, keep_intermediates):
+        """The per-detection heads after misc_bbox: here im_detect_mask."""
+        cfg = self.cfg
+        dets, dcls, dcnt = out["dets"], out["classes"], out["counts"]
         # the mask batch: F x DETECTIONS_PER_IM rows (padded to 64), built on the
         # device from the device counts -- no host read inside the step
         # (box_results_with_nms_and_limit keeps <= DETECTIONS_PER_IM per frame
@@ -243,9 +264,6 @@ class FramePipeline:
         # batch reads it); complete() drops it so a kept result does not pin ~1.5 GB
         out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
         self._mark("im_detect_mask")
-        if sync:
-            self.complete(out)
-        return out
 
     def _post_detections(self, dets, classes, counts):
         """Hook after box_results_with_nms_and_limit's device steps (the VOS loop
@@ -299,6 +317,122 @@ class FramePipeline:
         out["mask_rois"] = out["mask_rois"][:M]
         out["counts_host"] = counts
         return out
+
+
+class KeypointFramePipeline(FramePipeline):
+    """FramePipeline for the Keypoint R-CNN configs (FPN): after misc_bbox the step runs
+    im_detect_keypoints (lib/core/test.py:529-564) and keypoint_results (:858-874)
+    instead of the mask stage, all on the device:
+
+      vd_mask_rois (the keypoint RoI batch: same rows and order as the mask batch)
+      --> vd_roi_align_fpn KRCNN.ROI_XFORM_RESOLUTION --> Keypoint_Head (MFMA 3x3
+      convs) --> Keypoint_Outs (deconv + bilinear upsample, 56x56 logits)
+      --> vd_heatmaps_to_keypoints against the detection boxes as stored in dets.
+
+    out["keyps"] [M,4,K] rows (x, y, logit, prob) for the M = sum(counts)
+    detections in (frame, class, proposal) order; with keep_intermediates also
+    kps_heatmaps [M,K,S,S], kps_feat [M,C,P,P] and kps_boxes [M,4].  Stage marks:
+    im_detect_keypoints, misc_keypoints."""
+
+    def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
+                 det_cap=256, device="cuda"):
+        if not cfg.MODEL.KEYPOINTS_ON:
+            raise ValueError("KeypointFramePipeline needs a MODEL.KEYPOINTS_ON config")
+        if not cfg.FPN.FPN_ON or bool(cfg.get("VOS", False)):
+            raise NotImplementedError("KeypointFramePipeline: FPN configs only (no C4 / VOS)")
+        super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
+        self._ones_d = torch.ones((batch,), dtype=torch.float64, device=self.device)
+
+    def _keypoint_batch(self, pyr, krois, klvl, kboxes, fast):
+        """RoIAlign + head + outputs + decode of a padded batch (padding rows are zero
+        boxes: a 1 x 1 resized map, never read)."""
+        kc = self.cfg.KRCNN
+        head = self.model.Keypoint_Head
+        if fast and getattr(head, "nhwc_ready", False):
+            kfeat = ops.roi_align_fpn(pyr, self.roi_scales, krois, klvl, kc.ROI_XFORM_RESOLUTION,
+                                      kc.ROI_XFORM_SAMPLING_RATIO, out_layout="nhwc")
+            x = head.head_nhwc(kfeat)
+            kfeat = kfeat.permute(0, 3, 1, 2)
+        else:
+            kfeat = ops.roi_align_fpn(pyr, self.roi_scales, krois, klvl, kc.ROI_XFORM_RESOLUTION,
+                                      kc.ROI_XFORM_SAMPLING_RATIO)
+            x = head.head(kfeat)
+        heat = self.model.Keypoint_Outs(x).contiguous()
+        self._mark("im_detect_keypoints")
+        keyps = ops.heatmaps_to_keypoints(heat, kboxes, kc.INFERENCE_MIN_SIZE)
+        self._mark("misc_keypoints")
+        return keyps, heat, kfeat
+
+    def _keypoint_rows(self, out, im_scale_d, rows, row0=0):
+        """Rows [row0, row0 + rows) of the keypoint batch: the scaled RoIs with their
+        levels, and the same rows of dets unscaled -- vd_mask_rois at scale 1 copies
+        the stored boxes bit for bit (a float32 times 1.0 in float64), in the batch's
+        row order, zeros past the total."""
+        cfg = self.cfg
+        dets, dcls, dcnt = out["dets"], out["classes"], out["counts"]
+        krois, klvl, _, ktotal = ops.mask_rois(dets, dcls, dcnt, im_scale_d, rows,
+                                               cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL,
+                                               row0=row0)
+        stored = ops.mask_rois(dets, dcls, dcnt, self._ones_d[:dets.shape[0]], rows,
+                               cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL, row0=row0)[0]
+        return krois, klvl, stored[:, 1:5], ktotal
+
+    def _roi_heads(self, out, F, pyr, fast, im_scale_d, keep_intermediates):
+        krois, klvl, kboxes, ktotal = self._keypoint_rows(out, im_scale_d, self.mask_rows(F))
+        keyps, heat, kfeat = self._keypoint_batch(pyr, krois, klvl, kboxes, fast)
+        out["keyps"], out["kps_rois"], out["kps_total"] = keyps, krois, ktotal
+        out["_kps_keep"] = keep_intermediates
+        if keep_intermediates:
+            out.update(kps_heatmaps=heat, kps_feat=kfeat, kps_boxes=kboxes)
+        out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
+
+    def complete(self, out: dict) -> dict:
+        """FramePipeline.complete for the keypoint outputs: the one host read, the
+        rare rows past the padded batch, and the trim to the M real detections."""
+        if "counts_host" in out:
+            return out
+        counts = out["counts"].cpu().tolist()
+        ops.raise_on_failed_counts(counts)
+        if max(counts, default=0) > self.det_cap:
+            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
+        keys = ["keyps", "kps_rois"]
+        if out.pop("_kps_keep", False):
+            keys += ["kps_heatmaps", "kps_feat", "kps_boxes"]
+        M, cap = sum(counts), out["keyps"].shape[0]
+        if M > cap:  # rows [cap, M): a second, rare batch
+            extra = -(-(M - cap) // 64) * 64
+            r2, l2, b2, _ = self._keypoint_rows(out, out["_im_scale_d"], extra, row0=cap)
+            k2, h2, f2 = self._keypoint_batch(out["_pyr"], r2, l2, b2, out["_fast"])
+            more = {"keyps": k2, "kps_rois": r2, "kps_heatmaps": h2, "kps_feat": f2,
+                    "kps_boxes": b2}
+            for k in keys:
+                out[k] = torch.cat([out[k], more[k]])
+        out.pop("_pyr", None)
+        out.pop("_fast", None)
+        out.pop("_im_scale_d", None)
+        for k in keys:
+            out[k] = out[k][:M]
+        out["counts_host"] = counts
+        return out
+
+
+def frame_keypoints(pipe: "KeypointFramePipeline", out: dict, num_classes: int = None):
+    """keypoint_results (lib/core/test.py:858-874) for every frame of a completed
+    KeypointFramePipeline output: a list over frames of cls_keyps -- num_classes lists,
+    empty but for the person class's, which holds the frame's [4, K] float32 arrays
+    (x, y, logit, prob) in detection order."""
+    from . import keypoints
+    K = int(num_classes or pipe.cfg.MODEL.NUM_CLASSES)
+    pipe.complete(out)
+    person = keypoints.get_person_class_index()
+    kps = out["keyps"].cpu().numpy()
+    res, start = [], 0
+    for k in (int(c) for c in out["counts_host"]):
+        cls_keyps = [[] for _ in range(K)]
+        cls_keyps[person] = [kps[i] for i in range(start, start + k)]
+        res.append(cls_keyps)
+        start += k
+    return res
 
 
 class RaggedBatch:

@@ -201,22 +201,23 @@ def _wino4_grid_better(N: int, Cin: int, H: int, W: int) -> bool:
     return _wino4_grid_blocks(N, H, W) < cells
 
 
-def conv3x3_route(N: int, Cin: int, Cout: int, H: int, W: int, mosaic=True):
+def conv3x3_route(N: int, Cin: int, Cout: int, H: int, W: int, mosaic=True, wino4=True):
     """(algorithm, mosaic) the engine runs a 3x3 / stride-1 / pad-1 fp32 conv of an
     N x Cin x H x W channels_last batch with: ('wino4', None) -- Winograd F(4x4,3x3),
     csrc/conv3x3_wino4.hip, where _wino4_ok holds -- else ('wino', layout) -- Winograd
     F(2x2,3x3), csrc/conv3x3_wino.hip, from 2^12 output pixels where its blocks are
     >= 60 % real output (Cout % 64, Cin % 8) -- else ('igemm', None), the implicit
     GEMM (csrc/conv3x3.hip), from 2^18 pixels, else (None, None): MIOpen / CK.
-    One rule for the engine (_conv3x3_mfma) and the bench's executed-FLOP count."""
+    One rule for the engine (_conv3x3_mfma) and the bench's executed-FLOP count.
+    wino4=False leaves F(4x4) out (the keypoint head: its accuracy bound)."""
     npx = N * H * W
     mos, use = _pick_mosaic(N, H, W, mosaic)
     wino = (os.environ.get("VOSDET_CONV3X3_ALGO", CONV3X3_ALGO) == "wino" and Cout % 64 == 0
             and Cin % 8 == 0 and Cout > 0 and Cin <= ops.WINO_MAX_CIN)
-    w4 = _wino4_mode(N, Cin, Cout, H, W) if wino else None
+    w4 = _wino4_mode(N, Cin, Cout, H, W) if wino and wino4 else None
     if w4 is not None:
         return "wino4", (w4 or None)
-    if wino and mosaic and _wino4_pair_ok(N, Cin, Cout, H, W):
+    if wino and wino4 and mosaic and _wino4_pair_ok(N, Cin, Cout, H, W):
         return "wino4", ("grid" if _wino4_grid_better(N, Cin, H, W) else "pair")
     if wino and npx >= _WINO_MIN_PIXELS and use >= _WINO_MIN_BLOCK_USE:
         return "wino", mos
@@ -264,7 +265,7 @@ def _dilated2_ok(conv: nn.Conv2d, x) -> bool:
             and os.environ.get("VOSDET_CONV3X3_MFMA", "1") != "0")
 
 
-def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True):
+def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True, wino4=True):
     """conv (3x3, stride 1, pad 1) of a channels_last fp32 tensor on the
     hand-written MFMA kernels with the bias (+ ReLU) epilogue, or None where
     they do not apply (other geometry, VOSDET_CONV3X3_MFMA=0).  The algorithm
@@ -281,7 +282,8 @@ def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True):
     7 x 7 octets), batch-to-space."""
     if _dilated2_ok(conv, x):
         N, C, H, W = x.shape
-        algo, mos = conv3x3_route(4 * N, C, conv.weight.shape[0], H // 2, W // 2, mosaic)
+        algo, mos = conv3x3_route(4 * N, C, conv.weight.shape[0], H // 2, W // 2, mosaic,
+                                  wino4)
         if (algo == "wino4" and mos in ("pair", "grid", None)
                 and os.environ.get("VOSDET_DILATED_INPLACE", "1") != "0"):
             # the kernel reads / writes the sub-maps in place: no polyphase copies
@@ -298,7 +300,7 @@ def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True):
                 return y
         xs = x.permute(0, 2, 3, 1).reshape(N, H // 2, 2, W // 2, 2, C).permute(
             2, 4, 0, 1, 3, 5).reshape(4 * N, H // 2, W // 2, C).permute(0, 3, 1, 2)
-        y = _conv3x3_mfma_core(conv, xs, bias, relu, mosaic, as_plain=True)
+        y = _conv3x3_mfma_core(conv, xs, bias, relu, mosaic, as_plain=True, wino4=wino4)
         if y is None:
             return None
         Co = y.shape[1]
@@ -306,11 +308,11 @@ def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True):
             2, 3, 0, 4, 1, 5).reshape(N, H, W, Co).permute(0, 3, 1, 2)
         _count_route("dilated2")
         return y
-    return _conv3x3_mfma_core(conv, x, bias, relu, mosaic)
+    return _conv3x3_mfma_core(conv, x, bias, relu, mosaic, wino4=wino4)
 
 
 def _conv3x3_mfma_core(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True,
-                       as_plain=False):
+                       as_plain=False, wino4=True):
     """_conv3x3_mfma's body; as_plain: a dilation-2 / pad-2 conv taken as the pad-1 conv
     it is on polyphase sub-maps (the caller has split x)."""
     dil = (1, 1) if as_plain else conv.dilation
@@ -345,7 +347,7 @@ def _conv3x3_mfma_core(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True,
     key = (w.data_ptr(), w._version)
     b = conv.bias.detach() if (bias and conv.bias is not None) else None
     algo, mos = conv3x3_route(x.shape[0], x.shape[1], w.shape[0], x.shape[2], x.shape[3],
-                              mosaic)
+                              mosaic, wino4)
     if algo == "wino4":
         if getattr(conv, "_vd_u4_key", None) != key:
             conv._vd_u4 = ops.conv3x3_wino4_weight(w.detach())
@@ -1222,6 +1224,127 @@ class MaskRCNNOutputs(nn.Module):
         return torch.sigmoid(y)
 
 
+class RoiPoseHeadV1convX(nn.Module):
+    """keypoint_rcnn_heads.roi_pose_head_v1convX (:129-179): KRCNN.NUM_STACKED_CONVS x
+    (conv k x k + ReLU) at KRCNN.CONV_HEAD_DIM on the RoIAlign'ed keypoint RoIs."""
+
+    def __init__(self, dim_in, roi_xform, spatial_scale, cfg):
+        super().__init__()
+        self.roi_xform = roi_xform
+        self.spatial_scale = spatial_scale
+        self.cfg = cfg
+        kc = cfg.KRCNN
+        hid, ks = kc.CONV_HEAD_DIM, kc.CONV_HEAD_KERNEL
+        mods = []
+        for _ in range(kc.NUM_STACKED_CONVS):
+            mods += [nn.Conv2d(dim_in, hid, ks, 1, ks // 2), nn.ReLU(inplace=True)]
+            dim_in = hid
+        self.conv_fcn = nn.Sequential(*mods)
+        self.dim_out = hid
+
+    def head(self, x):
+        return self.conv_fcn(x)
+
+    def prepare(self):
+        self.nhwc_ready = True
+
+    # The eight chained convs run Winograd F(2x2,3x3) at every batch size.  F(4x4), which
+    # conv3x3_route would pick from 256 RoI maps up, puts the chain's error against float64
+    # at ~12x a direct float32 chain's (F(2x2): 2.4x; measured, DESIGN 4k), past the 4x
+    # this head is held to.  True times the F(4x4) route (tools/bench_keypoints.py).
+    wino4 = False
+
+    def head_nhwc(self, x_nhwc):
+        """x_nhwc: R x P x P x C RoI features -> R x D x P x P (channels_last memory):
+        every conv on the MFMA 3x3 kernels with the fused bias + ReLU epilogue
+        (conv3x3_route over the RoI maps as a mosaic), as the mask head's."""
+        x = x_nhwc.permute(0, 3, 1, 2)  # NCHW view, channels_last
+        for m in self.conv_fcn:
+            if isinstance(m, nn.Conv2d):
+                y = _conv3x3_mfma(m, x, relu=True, mosaic=True, wino4=self.wino4)
+                x = y if y is not None else _conv_epi(m, x)
+        return x
+
+    def forward(self, x, rpn_ret):
+        c = self.cfg.KRCNN
+        x = self.roi_xform(x, rpn_ret, blob_rois="keypoint_rois", method=c.ROI_XFORM_METHOD,
+                           resolution=c.ROI_XFORM_RESOLUTION, spatial_scale=self.spatial_scale,
+                           sampling_ratio=c.ROI_XFORM_SAMPLING_RATIO)
+        return self.head(x)
+
+
+def bilinear_upsample_filter(size: int) -> np.ndarray:
+    """The size x size bilinear interpolation filter of the FCN code (outer product of
+    a triangle of half-width ceil(size / 2) centred on the kernel), float64."""
+    half = (size + 1) // 2
+    centre = half - 1.0 if size % 2 else half - 0.5
+    tri = 1.0 - np.abs(np.arange(size, dtype=np.float64) - centre) / half
+    return np.outer(tri, tri)
+
+
+class BilinearInterpolation2d(nn.Module):
+    """lib/nn/modules/upsample.py:9-53: fixed bilinear up_scale-x upsampling as a
+    ConvTranspose2d (kernel 2 * up_scale, stride up_scale, padding up_scale / 2)
+    whose weight is the FCN bilinear filter on the channel diagonal and whose bias
+    is zero: fixed by construction, never loaded from a checkpoint."""
+
+    def __init__(self, channels: int, up_scale: int):
+        super().__init__()
+        assert up_scale % 2 == 0, "Scale should be even"
+        self.up_scale = int(up_scale)
+        ks = 2 * self.up_scale
+        self.upconv = nn.ConvTranspose2d(channels, channels, ks, stride=self.up_scale,
+                                         padding=self.up_scale // 2)
+        w = np.zeros((channels, channels, ks, ks), np.float32)
+        w[range(channels), range(channels)] = bilinear_upsample_filter(ks)
+        with torch.no_grad():
+            self.upconv.weight.copy_(torch.from_numpy(w))
+            self.upconv.bias.zero_()
+        self.upconv.weight.requires_grad_(False)
+        self.upconv.bias.requires_grad_(False)
+
+    def forward(self, x):
+        return self.upconv(x)
+
+
+class KeypointOutputs(nn.Module):
+    """keypoint_rcnn_heads.keypoint_outputs (:17-88): optional deconv + ReLU, the
+    per-keypoint heatmap predictor (ConvTranspose2d 2x with USE_DECONV_OUTPUT, else a
+    1x1 conv) and the fixed bilinear UP_SCALE upsampling; logits, no activation."""
+
+    def __init__(self, dim_in, cfg):
+        super().__init__()
+        kc = cfg.KRCNN
+        dk = kc.DECONV_KERNEL
+        self.use_deconv = bool(kc.USE_DECONV)
+        if self.use_deconv:
+            self.deconv = nn.ConvTranspose2d(dim_in, kc.DECONV_DIM, dk, 2, padding=dk // 2 - 1)
+            dim_in = kc.DECONV_DIM
+        if kc.USE_DECONV_OUTPUT:
+            self.classify = nn.ConvTranspose2d(dim_in, kc.NUM_KEYPOINTS, dk, 2,
+                                               padding=dk // 2 - 1)
+        else:
+            self.classify = nn.Conv2d(dim_in, kc.NUM_KEYPOINTS, 1, 1, 0)
+        self.upsample_heatmap = kc.UP_SCALE > 1
+        if self.upsample_heatmap:
+            self.upsample = BilinearInterpolation2d(kc.NUM_KEYPOINTS, kc.UP_SCALE)
+
+    def forward(self, x):
+        # transposed convolutions stay on MIOpen in this version; its deterministic
+        # solvers only, so a replayed step repeats its bits
+        cd = torch.backends.cudnn
+        prev, cd.deterministic = cd.deterministic, True
+        try:
+            if self.use_deconv:
+                x = F.relu(self.deconv(x), inplace=True)
+            x = self.classify(x)
+            if self.upsample_heatmap:
+                x = self.upsample(x)
+        finally:
+            cd.deterministic = prev
+        return x
+
+
 # cfg.FAST_RCNN.ROI_BOX_HEAD / cfg.MRCNN.ROI_MASK_HEAD names -> modules (the
 # reference resolves them with get_func, model_builder.py:33-49)
 BOX_HEADS = {"fast_rcnn_heads.roi_2mlp_head": Roi2MLPHead,
@@ -1230,6 +1353,7 @@ MASK_HEADS = {"mask_rcnn_heads.mask_rcnn_fcn_head_v1up4convs": (MaskHeadV1upXcon
               "mask_rcnn_heads.mask_rcnn_fcn_head_v1up": (MaskHeadV1upXconvs, 2),
               "mask_rcnn_heads.mask_rcnn_fcn_head_v1up4convs_gn": (MaskHeadV1upXconvsGN, 4),
               "mask_rcnn_heads.mask_rcnn_fcn_head_v1up_gn": (MaskHeadV1upXconvsGN, 2)}
+KEYPOINT_HEADS = {"keypoint_rcnn_heads.roi_pose_head_v1convX": RoiPoseHeadV1convX}
 
 
 class Generalized_RCNN(nn.Module):
@@ -1247,11 +1371,17 @@ class Generalized_RCNN(nn.Module):
             self.Conv_Body.dim_out, self.roi_feature_transform, roi_scales, cfg)
         self.Box_Outs = FastRCNNOutputs(self.Box_Head.dim_out, cfg.MODEL.NUM_CLASSES,
                                         cfg.MODEL.CLS_AGNOSTIC_BBOX_REG)
-        mk, nconv = MASK_HEADS[cfg.MRCNN.ROI_MASK_HEAD]
-        self.Mask_Head = mk(self.Conv_Body.dim_out, self.roi_feature_transform, roi_scales, cfg,
-                            nconv)
-        self.Mask_Outs = MaskRCNNOutputs(
-            self.Mask_Head.dim_out, cfg.MODEL.NUM_CLASSES if cfg.MRCNN.CLS_SPECIFIC_MASK else 1)
+        if cfg.MODEL.MASK_ON:  # model_builder.py:107-114
+            mk, nconv = MASK_HEADS[cfg.MRCNN.ROI_MASK_HEAD]
+            self.Mask_Head = mk(self.Conv_Body.dim_out, self.roi_feature_transform, roi_scales,
+                                cfg, nconv)
+            self.Mask_Outs = MaskRCNNOutputs(
+                self.Mask_Head.dim_out,
+                cfg.MODEL.NUM_CLASSES if cfg.MRCNN.CLS_SPECIFIC_MASK else 1)
+        if cfg.MODEL.KEYPOINTS_ON:  # model_builder.py:117-123
+            self.Keypoint_Head = KEYPOINT_HEADS[cfg.KRCNN.ROI_KEYPOINTS_HEAD](
+                self.Conv_Body.dim_out, self.roi_feature_transform, roi_scales, cfg)
+            self.Keypoint_Outs = KeypointOutputs(self.Keypoint_Head.dim_out, cfg)
         anchors = []
         k_min, k_max = cfg.FPN.RPN_MIN_LEVEL, cfg.FPN.RPN_MAX_LEVEL
         for lvl in range(k_min, k_max + 1):
@@ -1310,7 +1440,10 @@ class Generalized_RCNN(nn.Module):
         prepare_fpn_body(self.Conv_Body, epilogue)
         self.RPN.fuse()
         self.Box_Head.prepare()
-        self.Mask_Head.prepare()
+        if hasattr(self, "Mask_Head"):
+            self.Mask_Head.prepare()
+        if hasattr(self, "Keypoint_Head"):
+            self.Keypoint_Head.prepare()
         return self
 
 

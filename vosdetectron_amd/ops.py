@@ -1612,6 +1612,43 @@ def rle_strings(counts: torch.Tensor, n: torch.Tensor) -> list:
 
 
 # --------------------------------------------------------------------------- #
+# keypoint_results: heatmap decode                                             #
+# --------------------------------------------------------------------------- #
+KEYPOINT_MAX_HEATMAP = 64  # csrc/keypoints.hip kKpMaxM
+KEYPOINT_MAX_K = 32
+
+
+def heatmaps_to_keypoints(maps: torch.Tensor, boxes: torch.Tensor,
+                          min_size: int = 0) -> torch.Tensor:
+    """heatmaps_to_keypoints (lib/utils/keypoints.py:103-157) on the device
+    (vd_heatmaps_to_keypoints): maps [R,K,M,M] fp32 logits, boxes [R,>=4] fp32
+    (x1, y1, x2, y2 first; a column view such as dets[:, 1:5] is read in place by
+    its row stride) -> [R,4,K] fp32 rows (x, y, logit, prob).  No host read."""
+    m = _need(maps, "maps")
+    if m.dim() != 4 or m.shape[2] != m.shape[3]:
+        raise ValueError("maps must be R x K x M x M, got %s" % (tuple(maps.shape),))
+    R, K, M = m.shape[0], m.shape[1], m.shape[2]
+    if M < 1 or M > KEYPOINT_MAX_HEATMAP or K < 1 or K > KEYPOINT_MAX_K:
+        raise ValueError("heatmaps_to_keypoints: M = %d (<= %d), K = %d (<= %d)"
+                         % (M, KEYPOINT_MAX_HEATMAP, K, KEYPOINT_MAX_K))
+    if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda or boxes.dtype != torch.float32:
+        raise TypeError("boxes must be a float32 device tensor")
+    if boxes.dim() != 2 or boxes.shape[0] != R or boxes.shape[1] < 4:
+        raise ValueError("boxes must be R x >=4, got %s" % (tuple(boxes.shape),))
+    b = boxes
+    if b.stride(1) != 1 or (R > 1 and b.stride(0) < 4):
+        b = b.contiguous()
+    stride = b.stride(0) if R > 1 else 4  # one row: the stride is never applied
+    out = torch.empty((R, 4, K), dtype=torch.float32, device=m.device)
+    if R == 0:
+        return out
+    check(lib().vd_heatmaps_to_keypoints(m.data_ptr(), R, K, M, b.data_ptr(), int(stride),
+                                         int(min_size), out.data_ptr(), _stream()),
+          "vd_heatmaps_to_keypoints")
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # VOS temporal path: FlowAlign, GroupNorm epilogues, ConvGRU gates             #
 # --------------------------------------------------------------------------- #
 def _fmt(x: torch.Tensor, name: str) -> int:

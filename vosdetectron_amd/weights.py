@@ -12,7 +12,8 @@ there is no network).
    each frozen AffineChannel2d to whiten its input (what a trained BN does) and
    rescales the FPN / RPN convs to unit output; the heads get fixed gains
    (RPN objectness logits ~N(-1.5, 1.5^2), deltas ~0.2, class logits ~3x, mask
-   logits ~2x).  The result is a fixed dict that both the HIP engine and the
+   logits ~2x, keypoint heatmap logits 16x; the keypoint head's bilinear
+   upsampling filter is fixed by construction and never drawn).  The result is a fixed dict that both the HIP engine and the
    CPU oracle pipeline load, so both run the identical network.
 """
 from __future__ import annotations
@@ -27,7 +28,8 @@ def synthetic_state_dict(model: torch.nn.Module, seed: int = 0) -> dict:
     sd = {}
     for name, p in model.state_dict().items():
         shape = tuple(p.shape)
-        if "conv_flow_downsample" in name:  # frozen, fixed by construction
+        # frozen, fixed by construction (the keypoint head's bilinear upsampling filter)
+        if "conv_flow_downsample" in name or ".upsample.upconv." in name:
             sd[name] = p.detach().clone().cpu()
             continue
         is_affine = name.endswith(".weight") and len(shape) == 1
@@ -105,7 +107,12 @@ def calibrate(model, frame_u8: np.ndarray, device):
             del m._calibrated
     # fixed head gains (inputs are ~unit after the FPN calibration)
     model.Box_Outs.cls_score.weight.mul_(6.0)
-    model.Mask_Outs.classify.weight.mul_(4.0)
+    if hasattr(model, "Mask_Outs"):
+        model.Mask_Outs.classify.weight.mul_(4.0)
+    if hasattr(model, "Keypoint_Outs"):
+        # eight conv + ReLU layers at N(0, 1/fan_in) halve the variance each: the
+        # heatmap logits get the lost 2^4 back (spread of a few units)
+        model.Keypoint_Outs.classify.weight.mul_(16.0)
     return model
 
 
@@ -170,8 +177,10 @@ def build_model(cfg, seed: int = 0, device="cuda", fold=True, channels_last=Fals
         if c4:
             m.Box_Head.to(memory_format=torch.channels_last)
             m.Mask_Head.upconv5.to(memory_format=torch.channels_last)
-        else:
+        elif hasattr(m, "Mask_Head"):
             m.Mask_Head.conv_fcn.to(memory_format=torch.channels_last)
+        if hasattr(m, "Keypoint_Head"):
+            m.Keypoint_Head.conv_fcn.to(memory_format=torch.channels_last)
         if vos:
             m.ConvGRUs.to(memory_format=torch.channels_last)
     return m, sd
