@@ -597,10 +597,37 @@ int vd_nchw_to_nhwc(const float *in, int B, int C, int H, int W, float *out, voi
  * features: B x C x H x W (layout VD_LAYOUT_NCHW, the reference's) or
  * B x H x W x C (VD_LAYOUT_NHWC, C % 4 == 0); flow: B x 2 x H x W fp32 (x, y
  * displacement in level pixels, already downsampled by the module's
- * conv_flow_downsample); output: same layout/shape as features, written
+ * conv_flow_downsample, or produced from the raw flow by vd_flow_to_levels);
+ * output: same layout/shape as features, written
  * entirely (0 where the displaced position leaves [0, H-1) x [0, W-1)). */
 int vd_flow_align_forward(const float *features, const float *flow, int B, int C, int H, int W,
                           int layout, float *output, void *stream);
+
+/* Optical flow as read from the .flo file -> the level flows FlowAlign reads.
+ * Replaces
+ *   flo_to_blob (lib/utils/blob.py:63-75): prep_im_for_blob's cv2.resize(fx =
+ *     fy = im_scale, INTER_LINEAR) of the flow, `flo[0] * flo_scale` (a float32
+ *     array times a Python list: numpy multiplies in float64, the blob
+ *     assignment rounds once to float32), zero padding to FPN.COARSEST_STRIDE,
+ *     NCHW transpose;
+ *   FlowAlign.conv_flow_downsample (lib_vos/vos_model/flow_align/modules/
+ *     flow_align.py:12-25) of all five modules: a 2 -> 2 conv, kernel = stride
+ *     = k, diagonal weight (1/k)^3.
+ * raw_flow: F x H x W x 2 fp32 (u then v per pixel).  Hr, Wr = rint(H *
+ * im_scale), rint(W * im_scale); Hp, Wp the padded blob, both multiples of 64
+ * (VD_ERR_SHAPE otherwise).
+ *   blob(f,c,y,x)  = float(double(R(f,y,x,c)) * im_scale) for y < Hr, x < Wr, else 0
+ *   out_k(f,c,Y,X) = (1/k)^3 * sum of blob over the k x k block
+ * R is vd_image_resize_to_blob's resize on float input: identity at im_scale
+ * 1, the 2 x 2 area path at exactly 0.5, else the scalar float INTER_LINEAR
+ * (bit-exact against the numpy restatement; vs an executed cv2: unpinned).
+ * The block sums are added in a fixed tree (4 x 4 per thread, then 2 x 2 of
+ * the finer level; flow_prep.hip), so a value depends on its block alone.
+ * out_k: F x 2 x Hp/k x Wp/k, any may be NULL; blob: F x 2 x Hp x Wp (16-byte
+ * aligned) or NULL = never written.  One launch, no workspace, no atomics. */
+int vd_flow_to_levels(const float *raw_flow, int F, int H, int W, double im_scale, int Hr, int Wr,
+                      int Hp, int Wp, float *out4, float *out8, float *out16, float *out32,
+                      float *out64, float *blob, void *stream);
 
 /* Replaces flow_align_backward_cuda (flow_align_cuda.c:25-44, kernel :57-117).
  * NCHW only.  features_grad (B x C x H x W) and flow_grad (B x 2 x H x W) must

@@ -134,6 +134,8 @@ SIGNATURES = {
     "vd_heatmaps_to_keypoints": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     # VOS temporal path
     "vd_flow_align_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_flow_to_levels": (_I, [_P, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _P, _P, _P, _P, _P,
+                               _P, _P]),
     "vd_flow_align_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vd_group_norm_workspace_size": (_S, [_I, _I]),
     "vd_group_norm_act": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _I,

@@ -499,6 +499,15 @@ int vd_flow_align_forward(const float *features, const float *flow, int B, int C
                                  VD_STREAM(stream));
 }
 
+int vd_flow_to_levels(const float *raw_flow, int F, int H, int W, double im_scale, int Hr, int Wr,
+                      int Hp, int Wp, float *out4, float *out8, float *out16, float *out32,
+                      float *out64, float *blob, void *stream) {
+    if (!raw_flow) return VD_ERR_ARG;
+    float *const levels[5] = {out4, out8, out16, out32, out64};
+    return launch_flow_to_levels(raw_flow, F, H, W, im_scale, Hr, Wr, Hp, Wp, levels, blob,
+                                 VD_STREAM(stream));
+}
+
 int vd_flow_align_backward(const float *top_grad, const float *features, const float *flow,
                            int B, int C, int H, int W, float *features_grad, float *flow_grad,
                            void *stream) {

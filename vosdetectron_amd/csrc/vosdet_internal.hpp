@@ -183,6 +183,9 @@ struct GnApply {
     int mode, act, res_mode;
     float eps;
 };
+// raw .flo-layout flow -> blob-resolution flow + the five FlowAlign level flows (flow_prep.hip)
+int launch_flow_to_levels(const float *raw, int F, int H, int W, double im_scale, int Hr, int Wr,
+                          int Hp, int Wp, float *const levels[5], float *blob, hipStream_t s);
 int launch_flow_align_fwd(const float *feat, const float *flow, int B, int C, int H, int W,
                           int nhwc, float *out, hipStream_t s);
 int launch_flow_align_bwd(const float *top_diff, const float *feat, const float *flow, int B,

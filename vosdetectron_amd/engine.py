@@ -625,6 +625,31 @@ def frame_segms(pipe: FramePipeline, out: dict, num_classes: int = 81):
     return res
 
 
+def check_flow_args(flow, raw_flow, F, frame_hw, blob_hw, device):
+    """VOSPipeline.run's flow arguments: at most one of flow (blob resolution) and
+    raw_flow (F x H x W x 2 fp32 at frame resolution, on `device`); raw_flow needs
+    a blob whose sides are multiples of ops.FLOW_TILE.  ValueError names the
+    argument.  Needs no device."""
+    if raw_flow is None:
+        return
+    if flow is not None:
+        raise ValueError("VOSPipeline.run: give flow (blob resolution) or raw_flow (frame "
+                         "resolution), not both")
+    if not isinstance(raw_flow, torch.Tensor) or raw_flow.dtype != torch.float32:
+        raise ValueError("VOSPipeline.run: raw_flow must be a float32 tensor")
+    want = (int(F), int(frame_hw[0]), int(frame_hw[1]), 2)
+    if tuple(raw_flow.shape) != want:
+        raise ValueError("VOSPipeline.run: raw_flow must be F x H x W x 2 = %s at the "
+                         "pipeline's frame_hw, got %s" % (want, tuple(raw_flow.shape)))
+    if raw_flow.device.type != torch.device(device).type:
+        raise ValueError("VOSPipeline.run: raw_flow must be on the pipeline's device (%s), "
+                         "got %s" % (device, raw_flow.device))
+    Hp, Wp = blob_hw
+    if Hp % ops.FLOW_TILE or Wp % ops.FLOW_TILE:
+        raise ValueError("VOSPipeline.run: raw_flow needs a blob whose sides are multiples of "
+                         "%d; this configuration's is %d x %d" % (ops.FLOW_TILE, Hp, Wp))
+
+
 class VOSPipeline(FramePipeline):
     """The VOS frame loop (lib_vos/tools/infer_davis_sequential.py:134-149 driving
     Generalized_VOS_RCNN._forward, vos_model_builder.py:289-447) for F sequences
@@ -636,7 +661,7 @@ class VOSPipeline(FramePipeline):
     def __init__(self, model, cfg, frame_hw=(480, 854), batch=1, channels_last=False,
                  det_cap=256, device="cuda"):
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
-        self._flow = None
+        self._flow = self._raw_flow = None
         # each sequence row's previous-frame result (prev_cls_boxes of the
         # reference loop, train_davis_online.py:591-592), for NMS_SMALL_BOX_IOU
         F = batch
@@ -730,13 +755,27 @@ class VOSPipeline(FramePipeline):
 
     def backbone(self, frames):
         feats = super().backbone(frames)
-        return self.model.temporal_fusion(feats, self._flow)
+        return self.model.temporal_fusion(feats, self._flow, level_flows=self._level_flows())
+
+    def _level_flows(self):
+        """The step's raw flow as the five FlowAlign level flows [P6 .. P2] (one
+        vd_flow_to_levels launch), or None when nothing would read them: no raw
+        flow, the static model, or every hidden state still unset."""
+        if self._raw_flow is None or not self.cfg.CONVGRU.DYNAMIC_MODEL:
+            return None
+        if all(h is None for h in self.model.hidden_states):
+            return None
+        levels, _ = ops.flow_to_levels(self._raw_flow, self.im_scale, self.Hp, self.Wp)
+        return levels[::-1]  # FlowAligns[i]: strides 64, 32, 16, 8, 4
 
     @torch.no_grad()
-    def run(self, frames: torch.Tensor, flow: torch.Tensor = None, keep_intermediates=False,
-            sync: bool = True):
+    def run(self, frames: torch.Tensor, flow: torch.Tensor = None, raw_flow: torch.Tensor = None,
+            keep_intermediates=False, sync: bool = True):
         """frames: F x H x W x 3 u8 (frame t of each sequence); flow: optional
         F x 2 x Hp x Wp optical flow at blob resolution (flo_to_blob, data_flow);
+        raw_flow: instead of flow, the F x H x W x 2 fp32 flow as read from the .flo
+        files (flow_io.read_flo) at the pipeline's frame_hw, on the device -- it is
+        resized, scaled, padded and brought to the five levels in one launch;
         sync as FramePipeline.run (False: complete() reads the counts later).
         With TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU on, every step's result
         must pass through frame_results before the next step runs (the filter
@@ -746,10 +785,12 @@ class VOSPipeline(FramePipeline):
                 "VOSPipeline.run: the previous step's result has not been through "
                 "frame_results(); TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU need it as the "
                 "next frame's previous result (lib_vos/tools/vos_test.py:113-118, 845-860)")
-        self._flow = flow
+        check_flow_args(flow, raw_flow, int(frames.shape[0]), (self.H, self.W), (self.Hp, self.Wp),
+                        self.device)
+        self._flow, self._raw_flow = flow, raw_flow
         try:
             out = super().run(frames, keep_intermediates, sync=sync)
         finally:
-            self._flow = None
+            self._flow = self._raw_flow = None
         self._unfinalized = True
         return out

@@ -1692,6 +1692,47 @@ def flow_align(features: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
     return out
 
 
+FLOW_STRIDES = (4, 8, 16, 32, 64)  # the FlowAlign levels, finest first (P2 .. P6)
+FLOW_TILE = 64  # vd_flow_to_levels: one workgroup per 64 x 64 blob tile
+
+
+def flow_to_levels(raw_flow: torch.Tensor, im_scale: float, Hp: int, Wp: int,
+                   strides: Sequence[int] = FLOW_STRIDES, want_blob: bool = False):
+    """flo_to_blob (lib/utils/blob.py:63-75) + every FlowAlign.conv_flow_downsample
+    in one launch (vd_flow_to_levels).  raw_flow: F x H x W x 2 fp32 as read from
+    the .flo file (u then v per pixel); Hp, Wp: the padded blob size, multiples of
+    64.  Returns (levels, blob): levels[i] is the F x 2 x Hp/k x Wp/k flow of
+    strides[i] = k, blob the F x 2 x Hp x Wp data_flow when want_blob, else None."""
+    if not isinstance(raw_flow, torch.Tensor):
+        raise TypeError("raw_flow must be a torch.Tensor")
+    if raw_flow.dim() != 4 or raw_flow.shape[3] != 2 or min(raw_flow.shape) < 1:
+        raise ValueError("raw_flow must be F x H x W x 2, got %s" % (tuple(raw_flow.shape),))
+    Hp, Wp = int(Hp), int(Wp)
+    if Hp % FLOW_TILE or Wp % FLOW_TILE:
+        raise ValueError("flow_to_levels: the blob %dx%d is not a multiple of %d"
+                         % (Hp, Wp, FLOW_TILE))
+    strides = tuple(int(k) for k in strides)
+    if any(k not in FLOW_STRIDES for k in strides) or len(set(strides)) != len(strides):
+        raise ValueError("strides must be distinct values of %s, got %s" % (FLOW_STRIDES, strides))
+    if not im_scale > 0:
+        raise ValueError("im_scale must be positive, got %r" % (im_scale,))
+    rf = _need(raw_flow, "raw_flow")
+    F, H, W, _ = rf.shape
+    Hr, Wr = resized_hw(H, W, im_scale)
+    if Hr < 1 or Wr < 1 or Hp < Hr or Wp < Wr:
+        raise ValueError("blob %dx%d does not hold the resized flow %dx%d" % (Hp, Wp, Hr, Wr))
+    levels = [torch.empty((F, 2, Hp // k, Wp // k), dtype=torch.float32, device=rf.device)
+              for k in strides]
+    ptr = {k: t.data_ptr() for k, t in zip(strides, levels)}
+    blob = (torch.empty((F, 2, Hp, Wp), dtype=torch.float32, device=rf.device)
+            if want_blob else None)
+    check(lib().vd_flow_to_levels(rf.data_ptr(), F, H, W, float(im_scale), Hr, Wr, Hp, Wp,
+                                  *[ptr.get(k) for k in FLOW_STRIDES],
+                                  blob.data_ptr() if want_blob else None, _stream()),
+          "vd_flow_to_levels")
+    return levels, blob
+
+
 def flow_align_backward(grad_out, features, flow):
     g = _need(grad_out, "grad_out")
     f = _need(features, "features")

@@ -12,7 +12,10 @@ run on PyTorch-ROCm; everything between them is HIP:
     (the static model every frame; the first frame of a sequence) skips the four
     convolutions whose outputs are exactly zero (W*h, W*(h*r)) -- same result.
   * FlowAlign (lib_vos/vos_model/flow_align): vd_flow_align_forward warps the
-    hidden states by the (downsampled) optical flow.
+    hidden states by the (downsampled) optical flow.  The five level flows come
+    from the modules' conv_flow_downsample over a blob-resolution flow
+    (data_flow), or ready-made from the raw .flo flow by one vd_flow_to_levels
+    launch (level_flows, ops.flow_to_levels).
 """
 from __future__ import annotations
 
@@ -133,11 +136,20 @@ class Generalized_VOS_RCNN(Generalized_RCNN):
     def set_update_hidden_states(self, update=True):
         self.update_hidden_states = update
 
-    def temporal_fusion(self, blob_conv, data_flow=None, fused=None):
+    def temporal_fusion(self, blob_conv, data_flow=None, fused=None, level_flows=None):
         """vos_model_builder.py:318-345 on the FPN outputs [P6..P2]: warp the
         hidden states by the flow (dynamic model), run each level's ConvGRU from the
         finest (P2) to the coarsest, fusing each with the bilinear-downsampled finer
-        result; the fused levels become the new hidden states (dynamic model)."""
+        result; the fused levels become the new hidden states (dynamic model).
+        level_flows: instead of data_flow, the five flows already at the levels
+        (level_flows[i] for FlowAligns[i], strides 64 .. 4, as ops.flow_to_levels
+        makes them from the raw flow): each hidden state is warped by its flow
+        directly and conv_flow_downsample is bypassed."""
+        if data_flow is not None and level_flows is not None:
+            raise ValueError("temporal_fusion: give data_flow or level_flows, not both")
+        if level_flows is not None and len(level_flows) != 5:
+            raise ValueError("temporal_fusion: level_flows must hold 5 flows (P6 .. P2), got %d"
+                             % len(level_flows))
         cfg = self.cfg
         dynamic = cfg.CONVGRU.DYNAMIC_MODEL
         if fused is None:
@@ -145,6 +157,9 @@ class Generalized_VOS_RCNN(Generalized_RCNN):
         hs = self.hidden_states if dynamic else [None] * 5
         if dynamic and data_flow is not None:
             hs = [self.FlowAligns[i](hs[i], data_flow) if hs[i] is not None else None
+                  for i in range(5)]
+        elif dynamic and level_flows is not None:
+            hs = [ops.flow_align(hs[i], level_flows[i]) if hs[i] is not None else None
                   for i in range(5)]
         out = list(blob_conv)
         for i in range(4, -1, -1):
