@@ -245,14 +245,27 @@ int vd_conv3x3_wino4_bias_act(const float *X, int N, int H, int W, int C, const 
 int vd_conv3x3_wino4_mosaic_bias_act(const float *X, int N, int H, int W, int C, const float *U,
                                      int Cout, const float *bias, int relu, float *Y,
                                      void *stream);
-/* The same over N maps stacked in one column at a pitch of H + 1 rounded up to 4 rows
- * (each map padded by its own zeros), so the 16-row output blocks run on through the
- * stack: for heights that leave most of a map's last block row empty (50 x 84 res4 /
- * P4, 25 x 42 res5).  Bit-identical to vd_conv3x3_wino4_bias_act; VD_ERR_SHAPE when
- * N H W C >= 2^31. */
+/* The same over N maps stacked at a pitch of H + 1 rows and W + 1 columns, both rounded
+ * up to 4 (each map padded by its own zeros, every 4 x 4 tile inside one map), g maps
+ * per stack row, so the output blocks run on through the stack: for sizes that leave
+ * most of a map's last block row or column empty (50 x 84 res4 / P4, 25 x 42 res5).
+ * g and the block shape come from the block plan (below).  Bit-identical to
+ * vd_conv3x3_wino4_bias_act; VD_ERR_SHAPE when N H W C >= 2^31. */
 int vd_conv3x3_wino4_rows_bias_act(const float *X, int N, int H, int W, int C, const float *U,
                                    int Cout, const float *bias, int relu, float *Y,
                                    void *stream);
+/* The block plan of vd_conv3x3_wino4_bias_act (mode 0) and of the stacked entries
+ * (mode 1: vd_conv3x3_wino4_rows_bias_act, vd_conv3x3_wino4_grouped_bias_act with rows)
+ * on a device of n_cu compute units.  A workgroup computes a whole output block, so a
+ * launch's time follows its block count: the plan picks the block shape (wide 16 x 32
+ * or tall 32 x 16 pixels) and, in mode 1, the maps per stack row g that need the fewest
+ * rounds of workgroups, then the fewest blocks; ties keep wide, g = 1.  Every plan gives
+ * the same bits.  out = {shape (0 wide, 1 tall), g, spatial blocks, rounds}.  Needs no
+ * GPU.  VOSDET_WINO4_PLAN (read at every call and every launch): "0" wide, g = 1;
+ * "tall,<g>" / "wide,<g>" forced (g clamped to 1..min(N, 64); 1 in mode 0); unset
+ * automatic; anything else VD_ERR_ARG. */
+int vd_conv3x3_wino4_plan(int N, int H, int W, int C, int Cout, int mode, int n_cu,
+                          int out[4]);
 /* A grouped 3x3 convolution (ResNeXt's conv2, ResNet.py:246-294 with groups > 1; C
  * in = out channels, C / groups dividing 64) by the same F(4x4) kernel: every 64-channel
  * output block reads only the 64 input channels of its groups.  U =

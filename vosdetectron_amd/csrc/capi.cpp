@@ -205,6 +205,11 @@ int vd_conv3x3_wino4_rows_bias_act(const float *X, int N, int H, int W, int C, c
     return launch_conv3x3_wino4(X, N, H, W, C, U, Cout, bias, relu, Y, VD_STREAM(stream), 2);
 }
 
+int vd_conv3x3_wino4_plan(int N, int H, int W, int C, int Cout, int mode, int n_cu,
+                          int out[4]) {
+    return conv3x3_wino4_plan(N, H, W, C, Cout, mode, n_cu, out);
+}
+
 int vd_conv3x3_wino4_grouped_bias_act(const float *X, int N, int H, int W, int C,
                                       const float *U, int groups, const float *bias, int relu,
                                       float *Y, int rows, void *stream) {

@@ -46,7 +46,12 @@
 //   patch [2][18 rows][84 16-B slots]: pixel column C's two 4-channel halves at slots
 //     2C + C/2 + half (a pad slot every other pixel), so the 64 lanes of a transform
 //     read (8 tiles of a tile row x 8 channels) fall in 64 distinct banks.
+//
+// Block plan (round 7): the default form also comes as a tall block (8 x 4 tiles, 32 x 16
+// output pixels, TALL) and the stacked entries place g maps per stack row at tile-aligned
+// pitches; conv3x3_wino4_plan picks shape and g for the fewest blocks, bit-identical.
 #include <stdlib.h>
+#include <string.h>
 
 #include "common.hpp"
 #include "vosdet_internal.hpp"
@@ -164,11 +169,22 @@ __device__ unsigned long long g_wino4_stamps[kStampWg * 8 * kStampNch * 6];
 // PK (round 6, the default; VOSDET_WINO4_PK=0 keeps the scalar transform): the input
 // transform in packed fp32, bit-identical
 template <bool RELU, int PROBE, bool ACC = false, int VD = 1, bool STAMP = false, bool IL = false,
-          bool PK = false>
+          bool PK = false, bool TALL = false>
 __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
     const float *__restrict__ X, int N, int H, int W, int C, const float *__restrict__ U,
     int Cout, const float *__restrict__ bias, float *__restrict__ Y, int tby, int tbx,
-    int cb_per_xcd, int probe_hi, int mos, int gin) {
+    int cb_per_xcd, int probe_hi, int mos, int gin, int gph, int gpw) {
+    // TALL (the default form only; the block plan, launch_conv3x3_wino4): 8 x 4 tiles,
+    // 32 rows x 16 columns of output from a 34 x 18-pixel patch at 45 slots a row.  The
+    // tile numbering (8 wave + (lane >> 3)), V, the MFMA loop and the output transform
+    // are the 4 x 8 block's; tile t sits at tile row t >> 2, column t & 3 (t >> 3, t & 7
+    // there), so a transforming wave reads two tile rows x 4 tile columns x 8 channels:
+    // each 32-lane half (the ds_read_b32 conflict group) is one tile row, 4 x 8
+    // consecutive dwords at a 40-dword pitch = 32 distinct banks at any row pitch
+    constexpr int kTR = TALL ? 8 : k4TR, kTC = TALL ? 4 : k4TC;
+    constexpr int kPR = 4 * kTR + 2, kPC = 4 * kTC + 2, kRP = TALL ? 45 : k4RP;
+    static_assert(kPR * kRP <= k4PSlots && 2 * kPC + kPC / 2 - 1 <= kRP, "patch stage");
+    static_assert(!TALL || (ACC && PK && !PROBE && !STAMP && !IL), "TALL: default form only");
     // static, not dynamic: a > 64 KiB dynamic allocation is honoured by a direct launch
     // after hipFuncSetAttribute but not by the same launch captured into a hipGraph
     // (every replayed P2 conv came out unwritten, round 5)
@@ -192,25 +208,24 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
     // holds maps 2 sp (columns 0..15) and 2 sp + 1 (columns 16..31), each at the
     // origin of its 16 x 16 cell; taps outside a map read zero, so every output is
     // the map's own padded convolution, bit-identical to one map per block
-    // mos >= 4: row stack (vd_conv3x3_wino4_rows_bias_act) -- the N maps stacked at a
-    // pitch of hp = mos >> 2 rows (a multiple of 4, > H: every tile inside one map's
-    // pitch, the rows past a map zero), one image of N hp rows
     // mos == 3: octets -- maps of at most 7 x 7, eight per block in 8 x 8 cells (2 rows
     // of 4), map n + 4 (y >> 3) + (x >> 3)
     // (mos & 3) == 2: grid (vd_conv3x3_wino4_grid_bias_act, round 6) -- the maps at a
-    // pitch of (H + 1) x (W + 1) in rows of gG = mos >> 2 (map gG gy + gx at row gy,
-    // column gx), one zero row / column between neighbours: tiles straddle maps, taps
-    // in a separator or past the last map read zero and separator outputs are not
-    // stored, so every output is its map's own padded convolution (in other tile
-    // positions than one map per block: equal within Winograd rounding, not bitwise)
+    // pitch of gph x gpw in rows of gG = mos >> 2 (map gG gy + gx at row gy, column
+    // gx), taps in a separator or past the last map read zero and separator outputs
+    // are not stored, so every output is its map's own padded convolution.  At the
+    // pitch (H + 1) x (W + 1) -- one zero row / column between neighbours -- tiles
+    // straddle maps (other tile positions than one map per block: equal within
+    // Winograd rounding, not bitwise).  At pitches rounded up to 4 (the tile-aligned
+    // stack of vd_conv3x3_wino4_rows_bias_act; gG = 1: the row stack) every tile lies
+    // in one map at the offset it has with one map per block: bit-identical
     const bool pair = mos == 1, oct = mos == 3, grid = (mos & 3) == 2;
-    const int hp = (mos & 3) == 0 ? mos >> 2 : 0;
-    const int gG = grid ? mos >> 2 : 0, gPh = H + 1, gPw = W + 1;
-    if (sp >= (pair ? (N + 1) >> 1 : oct ? (N + 7) >> 3 : ((hp || grid) ? tby * tbx : N * tby * tbx))) return;
-    const int n = pair ? 2 * sp : oct ? 8 * sp : ((hp || grid) ? 0 : sp / (tby * tbx));
+    const int gG = grid ? mos >> 2 : 0, gPh = gph, gPw = gpw;
+    if (sp >= (pair ? (N + 1) >> 1 : oct ? (N + 7) >> 3 : (grid ? tby * tbx : N * tby * tbx))) return;
+    const int n = pair ? 2 * sp : oct ? 8 * sp : (grid ? 0 : sp / (tby * tbx));
     const int rem = (pair || oct) ? 0 : sp - n * tby * tbx;
     const int tyb = rem / tbx, txb = rem - (rem / tbx) * tbx;
-    const int oy0 = 4 * k4TR * tyb, ox0 = 4 * k4TC * txb;
+    const int oy0 = 4 * kTR * tyb, ox0 = 4 * kTC * txb;
     const int iy0 = oy0 - 1, ix0 = ox0 - 1;
     // gin (grouped, round 6): a workgroup's 64 output channels read only the 64 input
     // channels of their groups -- input channels 64 cb .. + 63 at pixel stride C, U the
@@ -251,7 +266,7 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
     for (int k = 0; k < kDK; ++k) {
         if (!ACC && wave >= 4) break;
         const int s = 64 * (wave + kDW * k) + lane;
-        const int R = s / k4RP, u = s - R * k4RP;
+        const int R = s / kRP, u = s - R * kRP;
         const int m = u / 5, r5 = u - 5 * m;
         const int Cc = 2 * m + (r5 >> 1), hf = r5 & 1;
         const int y = iy0 + R, x = ix0 + Cc;
@@ -260,10 +275,10 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
         // mosaic: cell x >> 4 (map n + cell), column x & 15 of that map
         const int cell = pair ? (x >> 4) : oct ? (x >> 3) : grid ? gx : 0;
         const int xm = pair ? (x & 15) : oct ? (x & 7) : grid ? x - gx * gPw : x;
-        // row stack: map y / hp, its row y % hp (octets: map row 4 (y >> 3), row y & 7)
-        const int mr = (hp && y >= 0) ? y / hp : (oct && y >= 0) ? 4 * (y >> 3) : grid ? gG * gy : 0;
-        const int ly = hp ? y - mr * hp : oct ? (y & 7) : grid ? y - gy * gPh : y;
-        const bool ok = R < k4PR && r5 < 4 && Cc < k4PC && (unsigned)ly < (unsigned)H &&
+        // octets: map row 4 (y >> 3), row y & 7
+        const int mr = (oct && y >= 0) ? 4 * (y >> 3) : grid ? gG * gy : 0;
+        const int ly = oct ? (y & 7) : grid ? y - gy * gPh : y;
+        const bool ok = R < kPR && r5 < 4 && Cc < kPC && (unsigned)ly < (unsigned)H &&
                         y >= 0 && x >= 0 && (unsigned)xm < (unsigned)W && n + cell + mr < N &&
                         (!oct || (cell < 4 && mr < 8)) && (!grid || gx < gG);
         const int64_t po = pph ? px_off(n + cell + mr, ly, xm) : px_off(cell + mr, ly, xm);
@@ -294,9 +309,11 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
     // ---- transform (waves 0-3): lane -> tile (tile row = wave, column tc = lane >> 3),
     // channel ci = lane & 7; reads pixel (4 tr + r, 4 tc + c), channel ci (slot
     // (4 tr + r) * 84 + 10 tc + 2 c + c / 2 + ci / 4, word ci % 4), writes V[pos][tile][ci]
+    // (TALL: tile row 2 wave + (lane >> 5), column (lane >> 3) & 3)
     const int ttc = lane >> 3, tci = lane & 7;
+    const int ttr = TALL ? 2 * wave + (ttc >> 2) : wave, ttx = TALL ? (ttc & 3) : ttc;
     const float *const tread =
-        reinterpret_cast<const float *>(pst) + ((4 * wave) * k4RP + 10 * ttc + (tci >> 2)) * 4 +
+        reinterpret_cast<const float *>(pst) + ((4 * ttr) * kRP + 10 * ttx + (tci >> 2)) * 4 +
         (tci & 3);
     // V[pos][tile][ch] (first form), or (ACC) V[pos][tg][q = ch / 2][j = tile % 16][ch & 1]
     // with the 32-dword row XOR-swizzled by 8 q: the MFMA waves' ds_read2st64_b64 (16-lane
@@ -317,8 +334,8 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
                 f2v x[6], y[6];
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
-                    x[r] = f2v{tp[(r * k4RP + 2 * c + (c >> 1)) * 4],
-                               tp[(r * k4RP + 2 * (c + 1) + ((c + 1) >> 1)) * 4]};
+                    x[r] = f2v{tp[(r * kRP + 2 * c + (c >> 1)) * 4],
+                               tp[(r * kRP + 2 * (c + 1) + ((c + 1) >> 1)) * 4]};
                 w4_bt6v(x, y);
 #pragma unroll
                 for (int a = 0; a < 6; ++a) t[a][c >> 1] = y[a];
@@ -343,7 +360,7 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
         for (int c = 0; c < 6; ++c) {
             float x[6], y[6];
 #pragma unroll
-            for (int r = 0; r < 6; ++r) x[r] = tp[(r * k4RP + 2 * c + (c >> 1)) * 4];
+            for (int r = 0; r < 6; ++r) x[r] = tp[(r * kRP + 2 * c + (c >> 1)) * 4];
             w4_bt6(x, y);
 #pragma unroll
             for (int a = 0; a < 6; ++a) t[a][c] = y[a];
@@ -410,7 +427,7 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
         float xc[6], tt[6][6];
         if (IL && xon) {
 #pragma unroll
-            for (int r = 0; r < 6; ++r) xc[r] = tpi[(r * k4RP) * 4];
+            for (int r = 0; r < 6; ++r) xc[r] = tpi[(r * kRP) * 4];
         }
         if (!IL && xon) {
             // probe_hi bit 1 (VOSDET_WINO4_PRIO=1): the transform at wave priority 1
@@ -473,7 +490,7 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
                     if (pp < 5) {
                         const int c = pp + 1;
 #pragma unroll
-                        for (int r = 0; r < 6; ++r) xc[r] = tpi[(r * k4RP + 2 * c + (c >> 1)) * 4];
+                        for (int r = 0; r < 6; ++r) xc[r] = tpi[(r * kRP + 2 * c + (c >> 1)) * 4];
                     }
                 } else if (xon && pp < 12) {  // row pp - 6 of (B^T d) B -> V
                     const int a = pp - 6;
@@ -565,11 +582,21 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
         __syncthreads();
     }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ACC: the last chunk's nine U reloads are still in flight, into ring registers the
+    // compiler takes for dead (it sees them written at the asm load).  The wait holds
+    // the ring as operands, so none of its registers is handed to a value computed
+    // above the wait -- the landing load would overwrite it (the tall block's build kept
+    // the epilogue's channel offset in one: a wild bias / output address)
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]),
+                   "+v"(u[6]), "+v"(u[7]), "+v"(u[8])
+                 :
+                 : "memory");
 
     // ---- output transform (lane-local): accumulator slot r of lane (j, q) holds output
     // channel 64 cb + 16 cg + 4 q + r of tile 16 tg + j
-    const int tile = 16 * tg + j, tr = tile >> 3, tc = tile & 7;
+    const int tile = 16 * tg + j;
+    const int tr = TALL ? tile >> 2 : tile >> 3, tc = TALL ? (tile & 3) : (tile & 7);
     const int co = cb * k4Co + 16 * cg + 4 * q;
     const float4 bv = bias ? *reinterpret_cast<const float4 *>(bias + co)
                            : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -594,17 +621,21 @@ __global__ __launch_bounds__(k4Threads) void conv3x3_wino4_kernel(
             for (int k = 0; k < 4; ++k) o[4 * i + k][r] = y[k];
         }
     }
+    // tile-aligned pitches (the stack): a tile's 4 rows / columns lie in one map, so its
+    // map row and column are one division each, not one per output row and column
+    const bool gal = grid && ((gPh | gPw) & 3) == 0;
+    const int gyt = gal ? (oy0 + 4 * tr) / gPh : 0, gxt = gal ? (ox0 + 4 * tc) / gPw : 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int yv = oy0 + 4 * tr + i;
-        const int gy = grid ? yv / gPh : 0;
-        const int mr = hp ? yv / hp : oct ? 4 * (yv >> 3) : grid ? gG * gy : 0;
-        const int yy = hp ? yv - mr * hp : oct ? (yv & 7) : grid ? yv - gy * gPh : yv;
+        const int gy = gal ? gyt : grid ? yv / gPh : 0;
+        const int mr = oct ? 4 * (yv >> 3) : grid ? gG * gy : 0;
+        const int yy = oct ? (yv & 7) : grid ? yv - gy * gPh : yv;
         if (yy >= H || n + mr >= N) continue;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int xc = ox0 + 4 * tc + k;
-            const int gx = grid ? xc / gPw : 0;
+            const int gx = gal ? gxt : grid ? xc / gPw : 0;
             const int ncell = pair ? n + (xc >> 4) : oct ? n + mr + (xc >> 3) : n + mr + gx;
             const int xx = pair ? (xc & 15) : oct ? (xc & 7) : grid ? xc - gx * gPw : xc;
             if (xx >= W || ncell >= N || (grid && gx >= gG)) continue;
@@ -974,11 +1005,110 @@ int launch_conv3x3_wino4_weight(const float *w, int Cout, int C, float *U, hipSt
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 
+// The block plan: which output block (wide 16 x 32, tall 32 x 16) and, for the stacked
+// entries, how many maps g per stack row.  A workgroup computes its whole block whether
+// or not the tiles lie inside a map and a launch runs for many rounds of workgroups, so
+// its time follows the block count.  The stack places map n at row (n / g) hp, column
+// (n % g) wp, hp = H + 1 and wp = W + 1 rounded up to 4: every tile inside one map at
+// the offset it has with one map per block, so every candidate is bit-identical.
+//   cost: rounds of workgroups over the CUs, then blocks; the candidates in the order
+//   (wide, 1), (wide, 2..), (tall, 1..) and only a strictly cheaper one replaces an
+//   earlier one, so today's layout (wide, g = 1) wins every tie.
+// A pure function of the shape, n_cu and VOSDET_WINO4_PLAN ("0": wide, g = 1;
+// "tall,<g>" / "wide,<g>": forced, g clamped to 1..N; unset: automatic), so a captured
+// graph replays the grid it was captured with.  mode 0: plain (shape only), 1: stack.
+constexpr int k4PlanMaxG = 64;
+
+int conv3x3_wino4_plan(int N, int H, int W, int C, int Cout, int mode, int n_cu, int out[4]) {
+    if (N < 1 || H < 1 || W < 1 || n_cu < 1 || mode < 0 || mode > 1 || !out) return VD_ERR_ARG;
+    if (!conv3x3_wino4_supported(C, Cout)) return VD_ERR_SHAPE;
+    const int ncb = Cout / k4Co;
+    const int hp = (H + 1 + 3) / 4 * 4, wp = (W + 1 + 3) / 4 * 4;
+    auto count = [&](int tall, int g) -> int64_t {
+        const int bh = tall ? 32 : 16, bw = tall ? 16 : 32;
+        if (!mode) return (int64_t)N * ((H + bh - 1) / bh) * ((W + bw - 1) / bw);
+        const int64_t rows = (int64_t)((N + g - 1) / g) * hp, cols = (int64_t)(g - 1) * wp + W;
+        return ((rows + bh - 1) / bh) * ((cols + bw - 1) / bw);
+    };
+    auto rounds = [&](int64_t b) { return (b * ncb + n_cu - 1) / n_cu; };
+    const int gmax = mode ? (N < k4PlanMaxG ? N : k4PlanMaxG) : 1;
+    int tall = 0, g = 1;
+    const char *e = getenv("VOSDET_WINO4_PLAN");
+    if (e && e[0]) {
+        if (!strcmp(e, "0")) {
+        } else if (!strncmp(e, "tall", 4) || !strncmp(e, "wide", 4)) {
+            tall = e[0] == 't';
+            if (e[4] == ',') {
+                char *end = nullptr;
+                const long v = strtol(e + 5, &end, 10);
+                if (end == e + 5 || *end || v < 1) return VD_ERR_ARG;
+                g = v > gmax ? gmax : (int)v;
+            } else if (e[4]) {
+                return VD_ERR_ARG;
+            }
+        } else {
+            return VD_ERR_ARG;
+        }
+    } else {
+        int64_t bb = count(0, 1), br = rounds(bb);
+        for (int t = 0; t < 2; ++t)
+            for (int c = 1; c <= gmax; ++c) {
+                const int64_t b = count(t, c), r = rounds(b);
+                if (r < br || (r == br && b < bb)) bb = b, br = r, tall = t, g = c;
+            }
+    }
+    const int64_t b = count(tall, g), r = rounds(b);
+    if (b > 0x7fffffff) return VD_ERR_SHAPE;
+    out[0] = tall, out[1] = g, out[2] = (int)b, out[3] = (int)r;
+    return VD_OK;
+}
+
+namespace {
+int w4_num_cus() {  // of the current device, asked once (every device of a box is alike)
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+            v > 0)
+            return v;
+        return 256;
+    }();
+    return n;
+}
+}  // namespace
+
 int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float *U, int Cout,
                          const float *bias, int relu, float *Y, hipStream_t s, int mos,
                          int groups) {
     if ((int64_t)N * H * W == 0) return VD_OK;
     if (!conv3x3_wino4_supported(C, Cout)) return VD_ERR_SHAPE;
+    // the form switches, read at every launch (a few us of host time), so one process
+    // can A/B the forms
+    static const int probe = [] {
+        const char *e = getenv("VOSDET_WINO4_PROBE");
+        return e ? atoi(e) & 15 : 0;
+    }();
+    static const int probe_hi = [] {
+        const char *e = getenv("VOSDET_WINO4_PROBE");
+        return e ? (atoi(e) >> 4) & 1 : 0;
+    }();
+    const char *pse = getenv("VOSDET_WINO4_PS");
+    const bool ps = pse && pse[0] == '1';
+    // the ACC form (hand-counted vmcnt, conflict-free V layout) is the default;
+    // VOSDET_WINO4_ACC=0 selects the first form (bit-identical, 2-6 % slower)
+    const char *acce = getenv("VOSDET_WINO4_ACC");
+    const bool acc = !(acce && acce[0] == '0');
+    // VOSDET_WINO4_VD (ACC form): V fragments read 1-3 positions ahead
+    const char *vde = getenv("VOSDET_WINO4_VD");
+    const int vd = vde ? atoi(vde) : 1;
+    const char *pke = getenv("VOSDET_WINO4_PK");
+    const bool pk = !(pke && pke[0] == '0');
+    const char *ste = getenv("VOSDET_WINO4_STAMP");
+    const char *ile = getenv("VOSDET_WINO4_IL");
+    // the block plan serves the default form alone; the research forms keep the wide
+    // block and one map per stack row
+    const bool plain_form = acc && pk && !probe && !ps && vd != 2 && vd != 3 &&
+                            !(ste && ste[0] == '1') && !(ile && (ile[0] == '1' || ile[0] == '2'));
     // grouped: C == Cout, 64 input channels per 64-channel output block (C / groups
     // divides 64); the pair / octet / grid mosaics stay dense-only
     // groups == -2: polyphase (X / Y are N / 4 maps of 2H x 2W; the N sub-maps of H x W
@@ -1001,14 +1131,21 @@ int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float
         return VD_ERR_SHAPE;
     if (mos == 1 && H <= 7 && W <= 7) mos = 3;  // octets: eight maps per block
     if (mos == 3 && (int64_t)8 * H * W * C >= ((int64_t)1 << 31)) return VD_ERR_SHAPE;
-    // the row stack: pitch = H + 1 rounded up to 4 (a zero row after every map), one
-    // image whose offsets stay 32-bit
-    const int hp = (H + 1 + 3) / 4 * 4;
-    if (mos == 2) {
-        if ((int64_t)N * H * W * C >= ((int64_t)1 << 31) || (int64_t)N * hp >= ((int64_t)1 << 30))
-            return VD_ERR_SHAPE;
-        mos = hp << 2;
+    // the tile-aligned stack: pitches H + 1 / W + 1 rounded up to 4 (zero rows / columns
+    // after every map), one image whose offsets stay 32-bit; the plain layout and the
+    // stack take their block shape (and the stack its maps per row) from the plan
+    const int hp = (H + 1 + 3) / 4 * 4, wp = (W + 1 + 3) / 4 * 4;
+    if (mos == 2 && ((int64_t)N * H * W * C >= ((int64_t)1 << 31) ||
+                     (int64_t)N * hp >= ((int64_t)1 << 30)))
+        return VD_ERR_SHAPE;
+    int tall = 0, sg = 1;
+    if (plain_form && (mos == 2 || (mos == 0 && gin != 2))) {
+        int pl[4];
+        const int st = conv3x3_wino4_plan(N, H, W, C, Cout, mos == 2, w4_num_cus(), pl);
+        if (st != VD_OK) return st;
+        tall = pl[0], sg = pl[1];
     }
+    const int bh = tall ? 32 : 4 * k4TR, bw = tall ? 16 : 4 * k4TC;
     // the grid: maps at a (H + 1) x (W + 1) pitch, g per mosaic row, g chosen for the
     // fewest 16 x 32 blocks (14 x 14: 32 maps = 480 columns = 15 blocks exactly)
     int gG = 0;
@@ -1024,11 +1161,18 @@ int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float
         if ((int64_t)(N + gG - 1) / gG * (H + 1) >= ((int64_t)1 << 30)) return VD_ERR_SHAPE;
     }
     const bool cells = mos == 1 || mos == 3;
-    const int tby = cells ? 1
-                    : gG ? (int)(((int64_t)(N + gG - 1) / gG * (H + 1) + 4 * k4TR - 1) / (4 * k4TR))
-                         : ((mos ? N * hp : H) + 4 * k4TR - 1) / (4 * k4TR);
-    const int tbx = cells ? 1 : ((gG ? gG * (W + 1) : W) + 4 * k4TC - 1) / (4 * k4TC);
-    if (gG) mos = (gG << 2) | 2;
+    int gph = H + 1, gpw = W + 1;  // the pitches of the grid path
+    int tby = cells ? 1 : (H + bh - 1) / bh, tbx = cells ? 1 : (W + bw - 1) / bw;
+    if (gG) {
+        tby = (int)(((int64_t)(N + gG - 1) / gG * gph + bh - 1) / bh);
+        tbx = (gG * gpw + bw - 1) / bw;
+        mos = (gG << 2) | 2;
+    } else if (mos == 2) {
+        gph = hp, gpw = wp;
+        tby = (int)(((int64_t)((N + sg - 1) / sg) * hp + bh - 1) / bh);
+        tbx = (int)(((int64_t)(sg - 1) * wp + W + bw - 1) / bw);
+        mos = (sg << 2) | 2;
+    }
     const int64_t nsp = mos == 1 ? ((int64_t)N + 1) / 2
                                  : mos == 3 ? ((int64_t)N + 7) / 8
                                             : (int64_t)(mos ? 1 : N) * tby * tbx;
@@ -1041,16 +1185,8 @@ int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float
     const int64_t blocks = cbx ? (nsp + 8 / ncb - 1) / (8 / ncb) * 8 : (nsp + 7) / 8 * 8 * ncb;
     if (blocks > 0x7fffffff) return VD_ERR_SHAPE;
     static_assert(k4LdsB <= VD_LDS_BYTES, "LDS");
-    static const int probe = [] {
-        const char *e = getenv("VOSDET_WINO4_PROBE");
-        return e ? atoi(e) & 15 : 0;
-    }();
-    static const int probe_hi = [] {
-        const char *e = getenv("VOSDET_WINO4_PROBE");
-        return e ? (atoi(e) >> 4) & 1 : 0;
-    }();
     typedef void (*kern_t)(const float *, int, int, int, int, const float *, int, const float *,
-                           float *, int, int, int, int, int, int);
+                           float *, int, int, int, int, int, int, int, int);
     static const kern_t table[2][16] = {
         {conv3x3_wino4_kernel<false, 0>, conv3x3_wino4_kernel<false, 1>,
          conv3x3_wino4_kernel<false, 2>, conv3x3_wino4_kernel<false, 3>,
@@ -1068,9 +1204,6 @@ int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float
          conv3x3_wino4_kernel<true, 10>, conv3x3_wino4_kernel<true, 11>,
          conv3x3_wino4_kernel<true, 12>, conv3x3_wino4_kernel<true, 13>,
          conv3x3_wino4_kernel<true, 14>, conv3x3_wino4_kernel<true, 15>}};
-    // read at every launch (a few us of host time), so one process can A/B the forms
-    const char *pse = getenv("VOSDET_WINO4_PS");
-    const bool ps = pse && pse[0] == '1';
     if (ps && !probe && !mos && !gin) {
         typedef void (*kps_t)(const float *, int, int, int, int, const float *, int,
                               const float *, float *, int, int, int);
@@ -1092,15 +1225,6 @@ int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float
                            Cout, bias, Y, tby, tbx, cbx);
         return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
     }
-    // the ACC form (hand-counted vmcnt, conflict-free V layout) is the default;
-    // VOSDET_WINO4_ACC=0 selects the first form (bit-identical, 2-6 % slower)
-    const char *acce = getenv("VOSDET_WINO4_ACC");
-    const bool acc = !(acce && acce[0] == '0');
-    // VOSDET_WINO4_VD (ACC form): V fragments read 1-3 positions ahead
-    const char *vde = getenv("VOSDET_WINO4_VD");
-    const int vd = vde ? atoi(vde) : 1;
-    const char *pke = getenv("VOSDET_WINO4_PK");
-    const bool pk = !(pke && pke[0] == '0');
     kern_t kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 1> : conv3x3_wino4_kernel<false, 0, true, 1>;
     if (pk)
         kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 1, false, false, true>
@@ -1111,20 +1235,21 @@ int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float
         kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 3> : conv3x3_wino4_kernel<false, 0, true, 3>;
     const char *pre = getenv("VOSDET_WINO4_PRIO");
     const int prio = (pre && pre[0] == '1') ? 2 : 0;
-    const char *ste = getenv("VOSDET_WINO4_STAMP");
     if (ste && ste[0] == '1')
         kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 1, true>
                     : conv3x3_wino4_kernel<false, 0, true, 1, true>;
-    const char *ile = getenv("VOSDET_WINO4_IL");
     if (ile && ile[0] == '1')
         kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 1, false, true>
                     : conv3x3_wino4_kernel<false, 0, true, 1, false, true>;
     if (ile && ile[0] == '2')  // interleaved + stamps
         kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 1, true, true>
                     : conv3x3_wino4_kernel<false, 0, true, 1, true, true>;
+    if (tall)  // only ever planned for the default form
+        kacc = relu ? conv3x3_wino4_kernel<true, 0, true, 1, false, false, true, true>
+                    : conv3x3_wino4_kernel<false, 0, true, 1, false, false, true, true>;
     const kern_t kern = (acc && !probe) ? kacc : table[relu ? 1 : 0][probe];
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(k4Threads), 0, s, X, N, H, W, C, U,
-                       Cout, bias, Y, tby, tbx, cbx, probe_hi | prio, mos, gin);
+                       Cout, bias, Y, tby, tbx, cbx, probe_hi | prio, mos, gin, gph, gpw);
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 

@@ -76,6 +76,9 @@ int launch_conv3x3_wino4_weight(const float *w, int Cout, int C, float *U, hipSt
 int launch_conv3x3_wino4(const float *X, int N, int H, int W, int C, const float *U, int Cout,
                          const float *bias, int relu, float *Y, hipStream_t s, int mos = 0,
                          int groups = 1);
+// the block plan of a launch_conv3x3_wino4 (mode 0: plain, 1: the stacked entries):
+// out = {shape (0 wide 16 x 32, 1 tall 32 x 16), maps per stack row, blocks, rounds}
+int conv3x3_wino4_plan(int N, int H, int W, int C, int Cout, int mode, int n_cu, int out[4]);
 int launch_conv3x3_wino_weight(const float *w, int Cout, int C, float *U, hipStream_t s);
 int launch_conv3x3_wino(const float *X, int N, int H, int W, int C, const float *U, int Cout,
                         const float *bias, int relu, float *Y, hipStream_t s, int seg_h = 0);

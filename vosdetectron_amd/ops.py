@@ -872,8 +872,9 @@ def conv3x3_wino4_bias_act(x: torch.Tensor, u: torch.Tensor, bias: Optional[torc
     """act(conv3x3(x, pad 1) + bias) on a channels_last fp32 tensor by Winograd
     F(4x4,3x3) (vd_conv3x3_wino4_bias_act); u from conv3x3_wino4_weight.  mosaic
     True / "pair": maps of at most 15 x 15 two per output block
-    (vd_conv3x3_wino4_mosaic_bias_act); "rows": the maps stacked in one column at a
-    4-row pitch (vd_conv3x3_wino4_rows_bias_act); both bit-identical.  "grid": the
+    (vd_conv3x3_wino4_mosaic_bias_act); "rows": the maps stacked at tile-aligned
+    pitches, block shape and maps per stack row from the block plan
+    (vd_conv3x3_wino4_rows_bias_act, conv3x3_wino4_plan); both bit-identical.  "grid": the
     maps as a 2-D grid at an (H + 1) x (W + 1) pitch (vd_conv3x3_wino4_grid_bias_act;
     equal within Winograd rounding).  groups > 1: a grouped conv (u from
     conv3x3_wino4_grouped_weight; mosaic False or "rows").  None for a shape the kernel
@@ -920,6 +921,17 @@ def conv3x3_wino4_bias_act(x: torch.Tensor, u: torch.Tensor, bias: Optional[torc
         return None
     check(st, "vd_conv3x3_wino4_bias_act (mosaic %r)" % (mosaic,))
     return out
+
+
+def conv3x3_wino4_plan(N: int, H: int, W: int, C: int, Cout: int, stacked: bool, n_cu: int):
+    """The block plan of a conv3x3_wino4_bias_act launch (vd_conv3x3_wino4_plan; no GPU
+    needed): (shape "wide" 16 x 32 / "tall" 32 x 16, maps per stack row, spatial blocks,
+    rounds of workgroups over n_cu compute units).  stacked: the "rows" entries (dense
+    or grouped), else the plain entry.  Honours VOSDET_WINO4_PLAN like the launch."""
+    out = (ctypes.c_int * 4)()
+    check(lib().vd_conv3x3_wino4_plan(int(N), int(H), int(W), int(C), int(Cout), int(bool(stacked)),
+                                      int(n_cu), out), "vd_conv3x3_wino4_plan")
+    return ("tall" if out[0] else "wide", int(out[1]), int(out[2]), int(out[3]))
 
 
 def conv3x3_wino4_dilated2_bias_act(x: torch.Tensor, u: torch.Tensor,
