@@ -797,6 +797,45 @@ int vd_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int
 int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                              int box_stride, int min_size, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * keypoint_results' OKS NMS (lib/utils/keypoints.py:225-266 nms_oks /
+ * compute_oks, applied per frame at lib/core/test.py:864-870 as a Python loop over
+ * numpy arrays on the host) on the device, for all F frames of a step in two
+ * stream-ordered launches with no host read.
+ *
+ * vd_nms_oks_frames: keyps [keyps_rows, 4, K] fp32 rows (x, y, logit, prob),
+ * frame-major as vd_heatmaps_to_keypoints writes them: frame f's rows start at the
+ * exclusive prefix sum of the non-negative counts; dets [F, D, 5], classes [F, D],
+ * counts [F] as vd_box_detections leaves them; K must be 17 (the reference's sigma
+ * table; VD_ERR_ARG otherwise) and D <= 512 (VD_ERR_SHAPE otherwise).  Per frame:
+ *   score[i] = mean of the 17 logits in float32 (numpy's pairwise order);
+ *   processing order = descending score, the HIGHER index first among equal
+ *     scores (numpy's order for n <= 16; for larger n the reference's tie order
+ *     is unspecified and this is the library's).  NaN logits are unsupported;
+ *   a kept row i drops every later row j with compute_oks(i, j) > thresh, where
+ *     only i's box area enters (csrc/oks_nms.hip restates the arithmetic).
+ * Outputs (the inputs are not modified): keep [F, D] int32 frame-local indices in
+ * kept order (-1 past the count), counts_out [F], dets_out [F, D, 5] and
+ * classes_out [F, D] the kept rows in kept order (zeros past the count), keyps_out
+ * [keyps_rows, 4, K] the kept rows compacted frame-major -- a frame's first row is
+ * the exclusive prefix sum of counts_out -- zeros past the total; scores_out
+ * [F, D] fp32 (may be NULL) the scores by input index.  A negative count is a
+ * per-frame failure code: it is copied to counts_out and the frame is empty.  Rows
+ * past keyps_rows are never read: a frame whose rows extend past the buffer is cut
+ * to the rows present (callers that can overflow run again on the full set).
+ * F == 0 launches nothing.
+ *
+ * vd_compute_oks: compute_oks of one source row (src_keypoints [4, K], src_roi
+ * [4] = x1, y1, x2, y2) against N destination rows dst_keypoints [N, 4, K] ->
+ * out [N] float64.  As in the reference the destination boxes and the
+ * visibility / prob row are not read. */
+int vd_nms_oks_frames(const float *keyps, int64_t keyps_rows, int K, const float *dets,
+                      const int32_t *classes, const int32_t *counts, int F, int D, double thresh,
+                      int32_t *keep, int32_t *counts_out, float *dets_out, int32_t *classes_out,
+                      float *keyps_out, float *scores_out, void *stream);
+int vd_compute_oks(const float *src_keypoints, const float *src_roi, const float *dst_keypoints,
+                   int N, int K, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

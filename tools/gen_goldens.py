@@ -28,6 +28,7 @@ Runtime-only import shims (nothing under /root/reference is modified):
 Usage: python tools/gen_goldens.py   (writes tests/golden/*.npz)
        python tools/gen_goldens.py vos_post   (only tests/golden/vos_post.npz)
        python tools/gen_goldens.py soft_nms   (only tests/golden/soft_nms.npz)
+       python tools/gen_goldens.py nms_oks    (only tests/golden/nms_oks.npz)
 """
 import os
 import sys
@@ -603,12 +604,117 @@ def gen_soft_nms_fixture():
           % (out["soft_count"], out["vote_count"], out["det_count"], max_voters))
 
 
+OKS_SIGMAS = (.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87,
+              .89, .89)
+
+
+def _clustered_poses(rng, n):
+    """n poses (kp [n,4,17] float32 rows x, y, logit, prob; rois [n,4]; cluster ids):
+    clusters of jittered copies of a base pose inside jittered copies of its box.
+    A copy's jitter is small (OKS against its base well above 0.3) or wide (well
+    below), so a cluster holds pairs on both sides of the threshold."""
+    k = max(1, n // 6)
+    cid = rng.integers(0, k, n) if n > 2 else np.zeros(n, np.int64)
+    xy = rng.uniform(0, 900, (k, 2))
+    wh = rng.uniform(40, 260, (k, 2))
+    base = xy[:, None, :] + rng.uniform(0, 1, (k, 17, 2)) * wh[:, None, :]
+    side = np.sqrt(wh[:, 0] * wh[:, 1])[cid]
+    jit = np.where(rng.uniform(0, 1, n) < 0.6, 0.015, 0.22) * side
+    pts = base[cid] + rng.normal(0, 1, (n, 17, 2)) * jit[:, None, None]
+    kp = np.zeros((n, 4, 17), np.float32)
+    kp[:, 0], kp[:, 1] = pts[..., 0], pts[..., 1]
+    kp[:, 2] = rng.normal(rng.uniform(0, 8, (n, 1)), 2.0, (n, 17))
+    kp[:, 3] = rng.uniform(0, 1, (n, 17))
+    b = np.hstack([xy[cid], xy[cid] + wh[cid]]) + rng.normal(0, 0.03, (n, 4)) * side[:, None]
+    return kp, b.astype(np.float32), cid.astype(np.int64)
+
+
+def gen_nms_oks_fixture():
+    """tests/golden/nms_oks.npz: the executed reference nms_oks / compute_oks
+    (lib/utils/keypoints.py:225-266) at the call site's threshold 0.3
+    (lib/core/test.py:866) on clustered poses, n in {1, 2, 12 (two exact score ties),
+    16, 17, 64, 65, 100, 256, 300}: inputs, keep, the scores np.mean gives, and every
+    ovr vector the loop evaluated (compute_oks wrapped to record its result).  vars is
+    keypoints.py:251-254's expression evaluated by this numpy.  Asserted here and again
+    by the tests on load: every evaluated ovr at least 1e-6 from the threshold;
+    adjacent sorted scores at least 16 ulp apart (but for the tie case); for n >= 16 a
+    same-cluster pair above and one below the threshold, and 1 < kept < n."""
+    install_shims()
+    import utils.keypoints as ref_kps
+    thresh = 0.3
+    rec = []
+    ref_compute = ref_kps.compute_oks
+
+    def recording(*a):
+        r = ref_compute(*a)
+        rec.append(np.array(r, np.float64))
+        return r
+    ref_kps.compute_oks = recording
+    out = {"thresh": np.float64(thresh),
+           "vars": (np.array(OKS_SIGMAS) / 10.0 * 2) ** 2}
+    cases = [(1, "plain"), (2, "plain"), (12, "ties"), (16, "plain"), (17, "plain"),
+             (64, "plain"), (65, "plain"), (100, "plain"), (256, "plain"), (300, "plain")]
+    for i, (n, kind) in enumerate(cases):
+        for attempt in range(200):  # seeds in order until the conditions hold
+            rng = np.random.default_rng(20261020 + 1000 * i + attempt)
+            kp, rois, cid = _clustered_poses(rng, n)
+            if kind == "ties":  # rows 7 and 9: the logits of rows 2 and 4, poses beside them
+                for a, b in ((2, 7), (4, 9)):
+                    kp[b, 2] = kp[a, 2]
+                    kp[b, :2] = kp[a, :2] + np.float32(0.25)
+                    rois[b], cid[b] = rois[a], cid[a]
+            sc = np.mean(kp[:, 2, :], axis=1)
+            ss = np.sort(sc)
+            gaps = np.diff(ss) / np.spacing(np.abs(ss[1:]))
+            del rec[:]
+            keep = ref_kps.nms_oks(kp, rois, thresh)
+            ovr = [r.copy() for r in rec]
+            flat = np.concatenate(ovr) if ovr else np.zeros(0)
+            ok = np.all(np.abs(flat - thresh) >= 1e-6)
+            if kind == "ties":
+                ok &= int((gaps == 0).sum()) == 2 and np.all(gaps[gaps != 0] >= 16)
+                # each tied pair is one pose twice: the later-processed one is dropped
+                ok &= all((a in keep) != (b in keep) for a, b in ((2, 7), (4, 9)))
+            elif n > 1:
+                ok &= np.all(gaps >= 16)
+            if n >= 16:
+                above = below = False
+                for r in range(n):
+                    same = np.flatnonzero(cid == cid[r])
+                    same = same[same != r]
+                    if len(same):
+                        v = ref_compute(kp[r], rois[r], kp[same], rois[same])
+                        above |= bool((v > thresh + 1e-6).any())
+                        below |= bool((v < thresh - 1e-6).any())
+                ok &= above and below and 1 < len(keep) < n
+            if ok:
+                break
+        else:
+            raise AssertionError("nms_oks fixture: no seed satisfies the conditions at n=%d" % n)
+        margin = float(np.abs(flat - thresh).min()) if flat.size else float("nan")
+        print("nms_oks case %d: n=%d %s seed+%d kept %d, %d ovr values, margin %.3g"
+              % (i, n, kind, attempt, len(keep), flat.size, margin))
+        out["kp_%d" % i], out["rois_%d" % i], out["cluster_%d" % i] = kp, rois, cid
+        out["kind_%d" % i] = np.array(kind)
+        out["keep_%d" % i] = np.asarray(keep, np.int64)
+        out["scores_%d" % i] = np.asarray(sc, np.float32)
+        out["ovr_%d" % i] = flat
+        out["ovr_len_%d" % i] = np.array([len(r) for r in ovr], np.int64)
+    ref_kps.compute_oks = ref_compute
+    out["count"] = np.int64(len(cases))
+    np.savez_compressed(os.path.join(OUT, "nms_oks.npz"), **out)
+    print("wrote nms_oks.npz: %d bytes" % os.path.getsize(os.path.join(OUT, "nms_oks.npz")))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["vos_post"]:
         gen_vos_post_fixture()
     elif sys.argv[1:] == ["soft_nms"]:
         gen_soft_nms_fixture()
+    elif sys.argv[1:] == ["nms_oks"]:
+        gen_nms_oks_fixture()
     else:
         main()
         gen_vos_post_fixture()
         gen_soft_nms_fixture()
+        gen_nms_oks_fixture()

@@ -133,6 +133,10 @@ SIGNATURES = {
     "vd_rle_strings": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     # keypoint_results (heatmap decode)
     "vd_heatmaps_to_keypoints": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
+    # keypoint_results (OKS NMS)
+    "vd_nms_oks_frames": (_I, [_P, _L, _I, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P,
+                               _P, _P, _P]),
+    "vd_compute_oks": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     # VOS temporal path
     "vd_flow_align_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_flow_to_levels": (_I, [_P, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _P, _P, _P, _P, _P,

@@ -157,7 +157,9 @@ UNSUPPORTED = (
     ("MODEL.USE_DELTA_FLOW", bool, "delta-flow VOS head, lib_vos/vos_modeling/vos_model_builder.py"),
     # Keypoint R-CNN is built for the FPN family with the v1convX head and the
     # plain per-box decode (engine.KeypointFramePipeline)
-    ("KRCNN.NMS_OKS", bool, "OKS NMS of keypoint_results, lib/core/test.py:864-870"),
+    ("KRCNN.NMS_OKS", bool, "OKS NMS of keypoint_results, lib/core/test.py:864-870, as a config "
+     "key: the device kernel is switched on by engine.KeypointFramePipeline(nms_oks=True), or "
+     "called as keypoints.nms_oks"),
     ("KRCNN.ROI_KEYPOINTS_HEAD", _WithCfg(lambda v, c: bool(c.MODEL.KEYPOINTS_ON) and v != KEYPOINT_HEAD),
      "keypoint head other than %s" % KEYPOINT_HEAD),
     ("MODEL.KEYPOINTS_ON", _WithCfg(lambda v, c: bool(v) and bool(c.MODEL.MASK_ON)),

@@ -695,6 +695,28 @@ int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float
                                         VD_STREAM(stream));
 }
 
+int vd_nms_oks_frames(const float *keyps, int64_t keyps_rows, int K, const float *dets,
+                      const int32_t *classes, const int32_t *counts, int F, int D, double thresh,
+                      int32_t *keep, int32_t *counts_out, float *dets_out, int32_t *classes_out,
+                      float *keyps_out, float *scores_out, void *stream) {
+    if (F == 0) return VD_OK;
+    if (!keyps || !dets || !classes || !counts || !keep || !counts_out || !dets_out ||
+        !classes_out || !keyps_out || K != 17 || F < 0 || D < 1 || keyps_rows < 0)
+        return VD_ERR_ARG;
+    return launch_nms_oks_frames(keyps, keyps_rows, K, dets, classes, counts, F, D, thresh, keep,
+                                 counts_out, dets_out, classes_out, keyps_out, scores_out,
+                                 VD_STREAM(stream));
+}
+
+int vd_compute_oks(const float *src_keypoints, const float *src_roi, const float *dst_keypoints,
+                   int N, int K, double *out, void *stream) {
+    if (N == 0) return VD_OK;
+    if (!src_keypoints || !src_roi || !dst_keypoints || !out || K != 17 || N < 0)
+        return VD_ERR_ARG;
+    return launch_compute_oks(src_keypoints, src_roi, dst_keypoints, N, K, out,
+                              VD_STREAM(stream));
+}
+
 int vd_bias_relu_maxpool(const float *x, const float *bias, int N, int C, int H, int W,
                          float *out, void *stream) {
     if (!x || !bias || !out || N < 0 || C < 0 || H < 0 || W < 0) return VD_ERR_ARG;

@@ -214,6 +214,15 @@ int launch_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, in
 int launch_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                                  int box_stride, int min_size, float *out, hipStream_t s);
 
+// keypoint_results' OKS NMS (oks_nms.hip)
+int launch_nms_oks_frames(const float *keyps, int64_t rows, int K, const float *dets,
+                          const int32_t *classes, const int32_t *counts, int F, int D,
+                          double thresh, int32_t *keep, int32_t *counts_out, float *dets_out,
+                          int32_t *classes_out, float *keyps_out, float *scores_out,
+                          hipStream_t s);
+int launch_compute_oks(const float *src_kp, const float *src_roi, const float *dst_kp, int N,
+                       int K, double *out, hipStream_t s);
+
 int launch_bias_relu_maxpool(const float *x, const float *bias, int N, int C, int H, int W,
                              float *out, hipStream_t s);
 int launch_rpn_head(const float *x, const float *conv_bias, const float *w, const float *b,

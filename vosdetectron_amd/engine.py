@@ -23,6 +23,7 @@ RaggedBatch on the device, vd_image_resize_to_blob_ragged builds the blob.
 KeypointFramePipeline runs the Keypoint R-CNN configs: after misc_bbox, the pose head
 and vd_heatmaps_to_keypoints (im_detect_keypoints + keypoint_results, test.py:97-107)
 take the mask stage's place; frame_keypoints groups the result as cls_keyps.
+KeypointFramePipeline(nms_oks=...) adds keypoint_results' OKS NMS (vd_nms_oks_frames).
 """
 from __future__ import annotations
 
@@ -332,14 +333,37 @@ class KeypointFramePipeline(FramePipeline):
     out["keyps"] [M,4,K] rows (x, y, logit, prob) for the M = sum(counts)
     detections in (frame, class, proposal) order; with keep_intermediates also
     kps_heatmaps [M,K,S,S], kps_feat [M,C,P,P] and kps_boxes [M,4].  Stage marks:
-    im_detect_keypoints, misc_keypoints."""
+    im_detect_keypoints, misc_keypoints.
+
+    nms_oks (None / False: off, every output as above; True: the reference's 0.3; a
+    float: that threshold) appends keypoint_results' OKS NMS (test.py:864-870) to the
+    step as ops.nms_oks_frames, with no host read.  It needs MODEL.NUM_CLASSES == 2:
+    the kept indices address cls_boxes[person], which is the frame's detections only
+    when person is the only class.  out["dets"], ["classes"], ["counts"] and ["keyps"]
+    are then the post-NMS rows in kept order (descending mean logit), as the reference
+    returns cls_boxes / cls_keyps; out["oks_keep"] [F,cap] holds the frame-local
+    pre-NMS indices (-1 past the count).  kps_rois, kps_heatmaps, kps_feat and
+    kps_boxes stay in pre-NMS row order; keep_intermediates adds dets_pre_oks,
+    classes_pre_oks, counts_pre_oks and keyps_pre_oks.  Stage mark: misc_oks_nms."""
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
-                 det_cap=256, device="cuda"):
+                 det_cap=256, device="cuda", nms_oks=None):
         if not cfg.MODEL.KEYPOINTS_ON:
             raise ValueError("KeypointFramePipeline needs a MODEL.KEYPOINTS_ON config")
         if not cfg.FPN.FPN_ON or bool(cfg.get("VOS", False)):
             raise NotImplementedError("KeypointFramePipeline: FPN configs only (no C4 / VOS)")
+        self.oks_thresh = None
+        if nms_oks is not None and nms_oks is not False:
+            if int(cfg.MODEL.NUM_CLASSES) != 2:
+                raise ValueError(
+                    "KeypointFramePipeline(nms_oks=%r) needs MODEL.NUM_CLASSES == 2 (person "
+                    "only), got %d: nms_oks' indices address cls_boxes[person]"
+                    % (nms_oks, int(cfg.MODEL.NUM_CLASSES)))
+            if det_cap > ops.OKS_MAX_D:
+                raise ValueError("KeypointFramePipeline(nms_oks=%r): det_cap = %d exceeds "
+                                 "OKS NMS's %d rows per frame" % (nms_oks, det_cap,
+                                                                  ops.OKS_MAX_D))
+            self.oks_thresh = 0.3 if nms_oks is True else float(nms_oks)  # test.py:866
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
         self._ones_d = torch.ones((batch,), dtype=torch.float64, device=self.device)
 
@@ -377,6 +401,14 @@ class KeypointFramePipeline(FramePipeline):
                                cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL, row0=row0)[0]
         return krois, klvl, stored[:, 1:5], ktotal
 
+    def _oks_nms(self, out, pre, keyps):
+        """keypoint_results' OKS NMS of the pre-NMS rows `pre` (dets, classes, counts)
+        with their raw keypoints: out's detections and keypoints become the kept rows."""
+        res = ops.nms_oks_frames(keyps, pre["dets"], pre["classes"], pre["counts"],
+                                 self.oks_thresh)
+        out.update(dets=res.dets, classes=res.classes, counts=res.counts, keyps=res.keyps,
+                   oks_keep=res.keep)
+
     def _roi_heads(self, out, F, pyr, fast, im_scale_d, keep_intermediates):
         krois, klvl, kboxes, ktotal = self._keypoint_rows(out, im_scale_d, self.mask_rows(F))
         keyps, heat, kfeat = self._keypoint_batch(pyr, krois, klvl, kboxes, fast)
@@ -385,33 +417,61 @@ class KeypointFramePipeline(FramePipeline):
         if keep_intermediates:
             out.update(kps_heatmaps=heat, kps_feat=kfeat, kps_boxes=kboxes)
         out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
+        if self.oks_thresh is not None:
+            pre = {k: out[k] for k in ("dets", "classes", "counts", "keyps")}
+            out["_oks_pre"] = pre
+            if keep_intermediates:
+                out.update({k + "_pre_oks": v for k, v in pre.items()})
+            self._oks_nms(out, pre, keyps)
+            self._mark("misc_oks_nms")
 
     def complete(self, out: dict) -> dict:
         """FramePipeline.complete for the keypoint outputs: the one host read, the
-        rare rows past the padded batch, and the trim to the M real detections."""
+        rare rows past the padded batch, and the trim to the M real detections.  With
+        nms_oks the read brings the pre- and post-NMS counts together: keyps, dets and
+        classes follow the post-NMS counts (counts_host), the kps_* tensors and the
+        *_pre_oks intermediates the pre-NMS ones (counts_pre_oks_host).  The overflow
+        batch then decodes the remaining rows and runs the NMS again on the full set,
+        replacing the step's result."""
         if "counts_host" in out:
             return out
-        counts = out["counts"].cpu().tolist()
-        ops.raise_on_failed_counts(counts)
-        if max(counts, default=0) > self.det_cap:
-            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
-        keys = ["keyps", "kps_rois"]
-        if out.pop("_kps_keep", False):
-            keys += ["kps_heatmaps", "kps_feat", "kps_boxes"]
-        M, cap = sum(counts), out["keyps"].shape[0]
+        pre = out.pop("_oks_pre", None)
+        if pre is None:
+            counts = before = out["counts"].cpu().tolist()
+        else:
+            F = out["counts"].numel()
+            both = torch.cat([pre["counts"], out["counts"]]).cpu().tolist()
+            before, counts = both[:F], both[F:]
+        ops.raise_on_failed_counts(before)
+        if max(before, default=0) > self.det_cap:
+            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, before))
+        keep = out.pop("_kps_keep", False)
+        keys = ["kps_rois"] + (["kps_heatmaps", "kps_feat", "kps_boxes"] if keep else [])
+        raw = out["keyps"] if pre is None else pre["keyps"]  # one row per detection
+        M, cap = sum(before), raw.shape[0]
         if M > cap:  # rows [cap, M): a second, rare batch
             extra = -(-(M - cap) // 64) * 64
-            r2, l2, b2, _ = self._keypoint_rows(out, out["_im_scale_d"], extra, row0=cap)
+            r2, l2, b2, _ = self._keypoint_rows(pre or out, out["_im_scale_d"], extra, row0=cap)
             k2, h2, f2 = self._keypoint_batch(out["_pyr"], r2, l2, b2, out["_fast"])
-            more = {"keyps": k2, "kps_rois": r2, "kps_heatmaps": h2, "kps_feat": f2,
-                    "kps_boxes": b2}
+            more = {"kps_rois": r2, "kps_heatmaps": h2, "kps_feat": f2, "kps_boxes": b2}
             for k in keys:
                 out[k] = torch.cat([out[k], more[k]])
+            raw = torch.cat([raw, k2])
+            if pre is not None:
+                self._oks_nms(out, pre, raw)
+                counts = out["counts"].cpu().tolist()
         out.pop("_pyr", None)
         out.pop("_fast", None)
         out.pop("_im_scale_d", None)
         for k in keys:
             out[k] = out[k][:M]
+        if pre is None:
+            out["keyps"] = raw[:M]
+        else:
+            out["keyps"] = out["keyps"][:sum(counts)]
+            out["counts_pre_oks_host"] = before
+            if keep:
+                out["keyps_pre_oks"] = raw[:M]
         out["counts_host"] = counts
         return out
 
@@ -420,7 +480,8 @@ def frame_keypoints(pipe: "KeypointFramePipeline", out: dict, num_classes: int =
     """keypoint_results (lib/core/test.py:858-874) for every frame of a completed
     KeypointFramePipeline output: a list over frames of cls_keyps -- num_classes lists,
     empty but for the person class's, which holds the frame's [4, K] float32 arrays
-    (x, y, logit, prob) in detection order."""
+    (x, y, logit, prob) in detection order (with nms_oks: the kept rows, grouped by
+    the post-NMS counts)."""
     from . import keypoints
     K = int(num_classes or pipe.cfg.MODEL.NUM_CLASSES)
     pipe.complete(out)

@@ -7,6 +7,7 @@ only -- all arithmetic happens in the HIP kernels.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import sys
@@ -1657,6 +1658,115 @@ def heatmaps_to_keypoints(maps: torch.Tensor, boxes: torch.Tensor,
     check(lib().vd_heatmaps_to_keypoints(m.data_ptr(), R, K, M, b.data_ptr(), int(stride),
                                          int(min_size), out.data_ptr(), _stream()),
           "vd_heatmaps_to_keypoints")
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# keypoint_results: OKS NMS                                                    #
+# --------------------------------------------------------------------------- #
+OKS_K = 17        # the reference's sigma table (csrc/oks_nms.hip kOksK)
+OKS_MAX_D = 512   # detections per frame (kOksMaxD)
+
+OksNmsResult = collections.namedtuple(
+    "OksNmsResult", ["keep", "counts", "dets", "classes", "keyps", "scores"])
+
+
+def _oks_arg(t, name: str, dtype, shape_ok, shape_text: str) -> None:
+    """Host checks of one argument, the device last, each a ValueError naming it."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != dtype:
+        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if not shape_ok(t):
+        raise ValueError("%s must be %s, got %s" % (name, shape_text, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+
+
+def _oks_device(named) -> None:
+    dev = None
+    for name, t in named:
+        if not t.is_cuda:
+            raise ValueError("%s must be a device (HIP) tensor; there is no CPU path" % name)
+        if dev is not None and t.device != dev:
+            raise ValueError("%s is on %s, not on %s like the other arguments"
+                             % (name, t.device, dev))
+        dev = t.device
+
+
+def nms_oks_frames(keyps: torch.Tensor, dets: torch.Tensor, classes: torch.Tensor,
+                   counts: torch.Tensor, thresh: float = 0.3,
+                   counts_host: Optional[Sequence[int]] = None) -> OksNmsResult:
+    """nms_oks (lib/utils/keypoints.py:225-266, applied at lib/core/test.py:864-870)
+    for all F frames of a step on the device (vd_nms_oks_frames), no host read.
+    keyps [rows, 4, 17] fp32 frame-major as heatmaps_to_keypoints writes them (frame
+    f's rows start at the prefix sum of the non-negative counts), dets [F, D, 5],
+    classes [F, D] int32, counts [F] int32; D <= 512.  Returns new tensors (the inputs
+    are not modified): keep [F, D] int32 frame-local indices in kept order (-1 past
+    the count), counts [F], dets / classes the kept rows in kept order, keyps
+    [rows, 4, 17] the kept rows compacted frame-major (zeros past the total) and
+    scores [F, D] the mean logits by input index.  Order: descending score, the
+    higher index first among equal scores.  counts_host, when the caller has the
+    counts on the host, lets the row total be checked against keyps here; the kernel
+    itself never reads past keyps' rows."""
+    _oks_arg(keyps, "keyps", torch.float32, lambda t: t.dim() == 3 and t.shape[1] == 4,
+             "rows x 4 x K")
+    if keyps.shape[2] != OKS_K:
+        raise ValueError("keyps: K = %d, OKS NMS needs K == %d (the COCO sigma table)"
+                         % (keyps.shape[2], OKS_K))
+    _oks_arg(dets, "dets", torch.float32, lambda t: t.dim() == 3 and t.shape[2] == 5,
+             "F x D x 5")
+    F, D = dets.shape[0], dets.shape[1]
+    _oks_arg(classes, "classes", torch.int32, lambda t: tuple(t.shape) == (F, D), "F x D")
+    _oks_arg(counts, "counts", torch.int32, lambda t: tuple(t.shape) == (F,), "F")
+    if D < 1 or D > OKS_MAX_D:
+        raise ValueError("dets: D = %d, OKS NMS supports 1 <= D <= %d" % (D, OKS_MAX_D))
+    rows = keyps.shape[0]
+    if counts_host is not None:
+        need = sum(max(int(c), 0) for c in counts_host)
+        if len(counts_host) != F or need > rows:
+            raise ValueError("keyps has %d rows, the counts %s need %d"
+                             % (rows, list(counts_host), need))
+    _oks_device([("keyps", keyps), ("dets", dets), ("classes", classes), ("counts", counts)])
+    dev = keyps.device
+    res = OksNmsResult(torch.empty((F, D), dtype=torch.int32, device=dev),
+                       torch.empty((F,), dtype=torch.int32, device=dev),
+                       torch.empty_like(dets), torch.empty_like(classes),
+                       torch.empty_like(keyps),
+                       torch.empty((F, D), dtype=torch.float32, device=dev))
+    if F == 0:
+        return res
+    check(lib().vd_nms_oks_frames(keyps.data_ptr(), rows, OKS_K, dets.data_ptr(),
+                                  classes.data_ptr(), counts.data_ptr(), F, D, float(thresh),
+                                  res.keep.data_ptr(), res.counts.data_ptr(),
+                                  res.dets.data_ptr(), res.classes.data_ptr(),
+                                  res.keyps.data_ptr(), res.scores.data_ptr(), _stream()),
+          "vd_nms_oks_frames")
+    return res
+
+
+def compute_oks(src_keypoints: torch.Tensor, src_roi: torch.Tensor,
+                dst_keypoints: torch.Tensor) -> torch.Tensor:
+    """compute_oks (lib/utils/keypoints.py:243-266) on the device (vd_compute_oks):
+    src_keypoints [4, 17] fp32, src_roi [>=4] fp32 (x1, y1, x2, y2 first), dst_keypoints
+    [N, 4, 17] fp32 -> [N] float64.  Only the source's box enters."""
+    _oks_arg(src_keypoints, "src_keypoints", torch.float32,
+             lambda t: t.dim() == 2 and t.shape[0] == 4, "4 x K")
+    if src_keypoints.shape[1] != OKS_K:
+        raise ValueError("src_keypoints: K = %d, OKS needs K == %d"
+                         % (src_keypoints.shape[1], OKS_K))
+    _oks_arg(src_roi, "src_roi", torch.float32, lambda t: t.dim() == 1 and t.shape[0] >= 4,
+             "a vector of >= 4")
+    _oks_arg(dst_keypoints, "dst_keypoints", torch.float32,
+             lambda t: t.dim() == 3 and tuple(t.shape[1:]) == (4, OKS_K), "N x 4 x %d" % OKS_K)
+    _oks_device([("src_keypoints", src_keypoints), ("src_roi", src_roi),
+                 ("dst_keypoints", dst_keypoints)])
+    N = dst_keypoints.shape[0]
+    out = torch.empty((N,), dtype=torch.float64, device=dst_keypoints.device)
+    if N:
+        check(lib().vd_compute_oks(src_keypoints.data_ptr(), src_roi.data_ptr(),
+                                   dst_keypoints.data_ptr(), N, OKS_K, out.data_ptr(),
+                                   _stream()), "vd_compute_oks")
     return out
 
 

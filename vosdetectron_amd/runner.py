@@ -38,9 +38,10 @@ class PendingGather:
     earlier `wait()` are NOT guarded -- they alias the buffer and show the
     later step's rows once it is reused."""
 
-    def __init__(self, work, gatherer, rbuf, slot, gen, over=None):
+    def __init__(self, work, gatherer, rbuf, slot, gen, over=None, over_keyps=None):
         self.work, self.g, self.rbuf, self.slot, self.gen = work, gatherer, rbuf, slot, gen
         self.over = over  # this rank's mask rows past mask_rows (not in the packet)
+        self.over_keyps = over_keyps  # likewise its keypoint rows past keyps_rows
 
     def wait(self, views: bool = True, clone: bool = False) -> Dict[str, torch.Tensor]:
         """Orders the caller's stream after the collective; returns the gathered
@@ -56,8 +57,29 @@ class PendingGather:
         v = self.g._views(self.rbuf)
         return {k: t.clone() for k, t in v.items()} if clone else v
 
-    def finish(self, masks_full: Optional[torch.Tensor] = None, clone: bool = False
-               ) -> Dict[str, torch.Tensor]:
+    def _extra(self, what, M, W, cap, row_shape, full, saved):
+        """The rows past `cap` of every rank, zero-padded to the largest overflow, in
+        one all_gather: [W, max_overflow, *row_shape]."""
+        g = self.g
+        over = [max(0, m - cap) for m in M]
+        mo = max(over)
+        rank = dist.get_rank() if g.collective else 0
+        mine = full[cap:M[rank]] if full is not None else saved
+        if over[rank] and (mine is None or mine.shape[0] != over[rank]):
+            raise RuntimeError("rank %d has %d %s rows past the packet, %s given"
+                               % (rank, over[rank], what, None if mine is None else mine.shape[0]))
+        dev = g.send[0].device
+        send = torch.zeros((mo,) + row_shape, dtype=torch.float32, device=dev)
+        if over[rank]:
+            send[:over[rank]].copy_(mine.reshape((-1,) + row_shape))
+        if not g.collective:
+            return send.view((1, mo) + row_shape)
+        recv = torch.empty((W, mo) + row_shape, dtype=torch.float32, device=dev)
+        dist.all_gather_into_tensor(recv.view(-1), send.view(-1))
+        return recv
+
+    def finish(self, masks_full: Optional[torch.Tensor] = None, clone: bool = False,
+               keyps_full: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """wait() plus the mask rows past the packet's mask_rows, on every rank.
         Collective: call it on all ranks for the same step.  After the packet
         lands every rank reads the gathered counts (one small D2H) and so takes
@@ -67,33 +89,23 @@ class PendingGather:
         the largest overflow, as views["masks_extra"] [W, max_overflow, R, R];
         frame_masks reads them.  masks_full: this rank's complete M-row masks
         (after FramePipeline.complete); default: the rows gather_async could not
-        pack."""
+        pack.  A keypoint section (keyps_k) is completed the same way, decided from
+        the same counts: views["keyps_extra"] [W, max_overflow, 4, K] from keyps_full
+        or the rows gather_async could not pack; frame_keyps reads them."""
         v = self.wait(clone=clone)
         g = self.g
-        if not g.with_masks:
+        if not g.with_masks and not g.K:
             return v
         W = v["counts"].shape[0] // g.F
-        M = v["counts"].view(W, g.F).to(torch.int64).sum(1).cpu().tolist()
-        over = [max(0, m - g.mask_rows) for m in M]
-        mo = max(over, default=0)
-        if mo == 0:
-            return v
-        rank = dist.get_rank() if g.collective else 0
-        mine = masks_full[g.mask_rows:M[rank]] if masks_full is not None else self.over
-        if over[rank] and (mine is None or mine.shape[0] != over[rank]):
-            raise RuntimeError("rank %d has %d mask rows past the packet, %s given"
-                               % (rank, over[rank], None if mine is None else mine.shape[0]))
-        dev = g.send[0].device
-        send = torch.zeros((mo, g.R, g.R), dtype=torch.float32, device=dev)
-        if over[rank]:
-            send[:over[rank]].copy_(mine.reshape(-1, g.R, g.R))
-        if g.collective:
-            recv = torch.empty((W, mo, g.R, g.R), dtype=torch.float32, device=dev)
-            dist.all_gather_into_tensor(recv.view(-1), send.view(-1))
-        else:
-            recv = send.view(1, mo, g.R, g.R)
+        # a negative count is a frame's failure code: no rows
+        M = v["counts"].view(W, g.F).to(torch.int64).clamp(min=0).sum(1).cpu().tolist()
         v = dict(v)
-        v["masks_extra"] = recv
+        if g.with_masks and max(M, default=0) > g.mask_rows:
+            v["masks_extra"] = self._extra("mask", M, W, g.mask_rows, (g.R, g.R), masks_full,
+                                           self.over)
+        if g.K and max(M, default=0) > g.keyps_rows:
+            v["keyps_extra"] = self._extra("keypoint", M, W, g.keyps_rows, (4, g.K), keyps_full,
+                                           self.over_keyps)
         return v
 
 
@@ -104,7 +116,12 @@ class ResultGatherer:
       dets [F, D, 5] | classes [F, D] (int32 bit-cast) | counts [F] (int32) |
       masks [mask_rows, R, R]  (the class-selected fp32 masks of the step's
                                 M = sum(counts) detections, frame-major, as the
-                                engine produces them; rows >= M are padding)
+                                engine produces them; rows >= M are padding) |
+      keyps [keyps_rows, 4, K] (with keyps_k = K: the (x, y, logit, prob) rows of
+                                the M detections, frame-major like the masks;
+                                with_masks=False and keyps_k=17 is the keypoint
+                                model's packet.  keyps_k = 0: no such section, the
+                                layout above byte for byte)
 
     Packing is three device copies (no host loop, no per-frame work): the
     engine's masks are already frame-contiguous, so a frame's rows start at the
@@ -127,14 +144,18 @@ class ResultGatherer:
     send slot is the result) only without one."""
 
     def __init__(self, frames_per_rank: int, det_cap: int, mask_res: int, world: int,
-                 device, with_masks: bool = True, mask_rows: Optional[int] = None):
+                 device, with_masks: bool = True, mask_rows: Optional[int] = None,
+                 keyps_k: int = 0, keyps_rows: Optional[int] = None):
         F, D, R = frames_per_rank, det_cap, mask_res
         self.F, self.D, self.R, self.world, self.with_masks = F, D, R, world, with_masks
         self.mask_rows = int(mask_rows if mask_rows is not None else F * 100) if with_masks else 0
+        self.K = int(keyps_k)
+        self.keyps_rows = int(keyps_rows if keyps_rows is not None else F * 100) if self.K else 0
         self.o_cls = F * D * 5
         self.o_cnt = self.o_cls + F * D
         self.o_msk = self.o_cnt + F
-        self.L = self.o_msk + self.mask_rows * R * R
+        self.o_kps = self.o_msk + self.mask_rows * R * R
+        self.L = self.o_kps + self.keyps_rows * 4 * self.K
         self.send = [torch.zeros((self.L,), device=device) for _ in range(2)]
         self.recv = [torch.zeros((world, self.L), device=device) for _ in range(2)]
         self.slot = 0
@@ -148,7 +169,7 @@ class ResultGatherer:
     def bytes_per_rank(self) -> int:
         return 4 * self.L
 
-    def _pack(self, buf, dets, classes, counts, masks):
+    def _pack(self, buf, dets, classes, counts, masks, keyps=None):
         buf[:self.o_cls].copy_(dets.reshape(-1))
         buf[self.o_cls:self.o_cnt].view(torch.int32).copy_(classes.reshape(-1))
         buf[self.o_cnt:self.o_msk].view(torch.int32).copy_(counts.reshape(-1))
@@ -156,6 +177,10 @@ class ResultGatherer:
             M = min(masks.shape[0], self.mask_rows)  # the rest: PendingGather.finish
             if M:
                 buf[self.o_msk:self.o_msk + M * self.R * self.R].copy_(masks[:M].reshape(-1))
+        if self.K:
+            M = min(keyps.shape[0], self.keyps_rows)  # the rest: PendingGather.finish
+            if M:
+                buf[self.o_kps:self.o_kps + M * 4 * self.K].copy_(keyps[:M].reshape(-1))
 
     def _views(self, rb):
         W, F, D, R = rb.shape[0], self.F, self.D, self.R
@@ -165,8 +190,11 @@ class ResultGatherer:
                         .reshape(W * F, D),
              "counts": counts.reshape(W * F)}
         if self.with_masks:
-            v["masks"] = rb[:, self.o_msk:].reshape(W, self.mask_rows, R, R)
+            v["masks"] = rb[:, self.o_msk:self.o_kps].reshape(W, self.mask_rows, R, R)
             v["mask_offsets"] = self.frame_offsets(counts)
+        if self.K:
+            v["keyps"] = rb[:, self.o_kps:].reshape(W, self.keyps_rows, 4, self.K)
+            v["keyps_offsets"] = self.frame_offsets(counts.clamp(min=0))
         return v
 
     @staticmethod
@@ -177,24 +205,34 @@ class ResultGatherer:
         return torch.cumsum(c, 1) - c
 
     def gather_async(self, dets: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor,
-                     masks: torch.Tensor, counts_host: Optional[List[int]] = None
-                     ) -> PendingGather:
+                     masks: Optional[torch.Tensor] = None,
+                     counts_host: Optional[List[int]] = None,
+                     keyps: Optional[torch.Tensor] = None) -> PendingGather:
         """dets [F,D,5], classes [F,D] int32, counts [F] int32, masks [M,R,R] (the
-        engine's class-selected masks, frame-major).  counts_host is unused (kept
-        for callers of the round-1 signature)."""
+        engine's class-selected masks, frame-major; unused with with_masks=False),
+        keyps [M,4,K] (with keyps_k: the engine's keypoints, frame-major).
+        counts_host is unused (kept for callers of the round-1 signature)."""
+        if self.with_masks and masks is None:
+            raise ValueError("gather_async: masks is required (the gatherer has a mask section)")
+        if self.K and (keyps is None or tuple(keyps.shape[1:]) != (4, self.K)):
+            raise ValueError("gather_async: keyps must be M x 4 x %d, got %s"
+                             % (self.K, None if keyps is None else tuple(keyps.shape)))
         s = self.slot
         self.slot ^= 1
         self.gen[s] += 1
-        self._pack(self.send[s], dets, classes, counts, masks)
+        self._pack(self.send[s], dets, classes, counts, masks, keyps)
         over = masks[self.mask_rows:] if self.with_masks and masks.shape[0] > self.mask_rows \
             else None
+        over_k = keyps[self.keyps_rows:] if self.K and keyps.shape[0] > self.keyps_rows else None
         if not self.collective:
-            return PendingGather(None, self, self.send[s].view(1, -1), s, self.gen[s], over)
+            return PendingGather(None, self, self.send[s].view(1, -1), s, self.gen[s], over,
+                                 over_k)
         work = dist.all_gather_into_tensor(self.recv[s].view(-1), self.send[s], async_op=True)
-        return PendingGather(work, self, self.recv[s], s, self.gen[s], over)
+        return PendingGather(work, self, self.recv[s], s, self.gen[s], over, over_k)
 
-    def gather(self, dets, classes, counts, masks, counts_host=None) -> Dict[str, torch.Tensor]:
-        return self.gather_async(dets, classes, counts, masks).wait()
+    def gather(self, dets, classes, counts, masks=None, counts_host=None, keyps=None
+               ) -> Dict[str, torch.Tensor]:
+        return self.gather_async(dets, classes, counts, masks, keyps=keyps).wait()
 
 
 def frame_masks(views: Dict[str, torch.Tensor], frames_per_rank: int, frame: int
@@ -213,6 +251,25 @@ def frame_masks(views: Dict[str, torch.Tensor], frames_per_rank: int, frame: int
         raise RuntimeError("frame %d's masks (rows %d..%d) exceed the %d gathered mask rows "
                            "(PendingGather.finish ships the rest)" % (frame, o, o + k, cap))
     head = views["masks"][r, o:cap] if o < cap else views["masks"][r, :0]
+    return torch.cat([head, extra[r, max(0, o - cap):o + k - cap]])
+
+
+def frame_keyps(views: Dict[str, torch.Tensor], frames_per_rank: int, frame: int
+                ) -> torch.Tensor:
+    """The gathered keypoints [k, 4, K] of global frame index `frame` (rank-major
+    order), like frame_masks: rows past the packet's keypoint rows come from
+    views["keyps_extra"] (PendingGather.finish), and raise if the views lack them."""
+    r, f = divmod(frame, frames_per_rank)
+    o = int(views["keyps_offsets"][r, f])
+    k = max(int(views["counts"][frame]), 0)
+    cap = views["keyps"].shape[1]
+    if o + k <= cap:
+        return views["keyps"][r, o:o + k]
+    extra = views.get("keyps_extra")
+    if extra is None or o + k - cap > extra.shape[1]:
+        raise RuntimeError("frame %d's keypoints (rows %d..%d) exceed the %d gathered rows "
+                           "(PendingGather.finish ships the rest)" % (frame, o, o + k, cap))
+    head = views["keyps"][r, o:cap] if o < cap else views["keyps"][r, :0]
     return torch.cat([head, extra[r, max(0, o - cap):o + k - cap]])
 
 
