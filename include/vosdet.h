@@ -642,6 +642,49 @@ int vd_flow_to_levels(const float *raw_flow, int F, int H, int W, double im_scal
                       int Hp, int Wp, float *out4, float *out8, float *out16, float *out32,
                       float *out64, float *blob, void *stream);
 
+/* The delta-flow head of Generalized_VOS_RCNN (MODEL.USE_DELTA_FLOW,
+ * lib_vos/vos_modeling/vos_model_builder.py:95-104, 314-326), step 1: for every
+ * level l, frame b and pixel
+ *   new   = tanh(sum over the 3 x 3 taps and C channels of w * x)   (zero padding)
+ *   delta = valid[b] ? new - feat : 0     (one IEEE subtraction of the stored value)
+ *   feat  = new
+ * in one launch for all levels.  features: B x C x H x W (VD_LAYOUT_NCHW) or
+ * B x H x W x C (VD_LAYOUT_NHWC), 16-byte aligned; weight: the Conv2d weight
+ * [2][C][3][3] repacked to [18][C], row (ky * 3 + kx) * 2 + o, 16-byte aligned;
+ * feat (the state, updated in place: the thread that writes an element is the
+ * one that read it) and delta: B x 2 x H x W.  valid: B int32 on the device.
+ * `levels` is a host array read at the call (its contents travel as kernel
+ * arguments); the launch reads no host value that changes between steps, so a
+ * captured step replays.  C % 64 == 0 and C <= 512 (VD_ERR_SHAPE otherwise);
+ * any H, W >= 1.  The sum is float32 fused multiply-adds in a fixed order
+ * (delta_flow.hip); tanh is the device tanhf. */
+typedef struct {
+    const float *features;
+    int H;
+    int W;
+    const float *weight;
+    float *feat;
+    float *delta;
+} VdDeltaFlowLevel;
+
+int vd_delta_flow_features(const VdDeltaFlowLevel *levels, int num_levels, int B, int C,
+                           int layout, const int32_t *valid, void *stream);
+
+/* Step 2: the five deltas (strides 64, 32, 16, 8, 4; d_k is B x 2 x Hp/k x Wp/k)
+ * -> the five FlowAlign level flows and, optionally, the blob-resolution flow:
+ *   data_flow(y, x) = sum over k = 64, 32, 16, 8, 4 in that order of
+ *                     bilinear_up(d_k)(y, x) * k      (align_corners False: source
+ *                     max((dst + 0.5) / k - 0.5, 0), upper tap clamped)
+ *   out_k(Y, X)     = (1/k)^3 * sum of data_flow over the k x k block
+ * i.e. F.interpolate + division by the scale + the modules' conv_flow_downsample.
+ * The block sums are added in a fixed tree, so a value depends on its block
+ * alone.  Hp, Wp multiples of 64 (VD_ERR_SHAPE otherwise).  out_k may be NULL;
+ * blob: B x 2 x Hp x Wp (16-byte aligned) or NULL = never written.  One launch,
+ * no workspace, no atomics. */
+int vd_delta_flow_to_levels(const float *d64, const float *d32, const float *d16, const float *d8,
+                            const float *d4, int B, int Hp, int Wp, float *out64, float *out32,
+                            float *out16, float *out8, float *out4, float *blob, void *stream);
+
 /* Replaces flow_align_backward_cuda (flow_align_cuda.c:25-44, kernel :57-117).
  * NCHW only.  features_grad (B x C x H x W) and flow_grad (B x 2 x H x W) must
  * be zero-filled by the caller (functions/flow_align.py:36-39); contributions

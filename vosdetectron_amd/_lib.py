@@ -42,6 +42,12 @@ class VdRpnLevel(ctypes.Structure):
                 ("W", ctypes.c_int), ("spatial_scale", ctypes.c_float)]
 
 
+class VdDeltaFlowLevel(ctypes.Structure):
+    _fields_ = [("features", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("weight", ctypes.c_void_p), ("feat", ctypes.c_void_p),
+                ("delta", ctypes.c_void_p)]
+
+
 class VdFrameGeom(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_int64), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("Hr", ctypes.c_int32), ("Wr", ctypes.c_int32), ("inv_scale", ctypes.c_double)]
@@ -141,6 +147,8 @@ SIGNATURES = {
     "vd_flow_align_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_flow_to_levels": (_I, [_P, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _P, _P, _P, _P, _P,
                                _P, _P]),
+    "vd_delta_flow_features": (_I, [ctypes.POINTER(VdDeltaFlowLevel), _I, _I, _I, _I, _P, _P]),
+    "vd_delta_flow_to_levels": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vd_flow_align_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vd_group_norm_workspace_size": (_S, [_I, _I]),
     "vd_group_norm_act": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _I,

@@ -154,7 +154,9 @@ UNSUPPORTED = (
     ("TEST.BBOX_AUG.ENABLED", bool, "box test-time augmentation, lib/core/test.py:193-727"),
     ("TEST.MASK_AUG.ENABLED", bool, "mask test-time augmentation, lib/core/test.py:405-480"),
     ("TEST.KPS_AUG.ENABLED", bool, "keypoint test-time augmentation (keypoint heads out of scope)"),
-    ("MODEL.USE_DELTA_FLOW", bool, "delta-flow VOS head, lib_vos/vos_modeling/vos_model_builder.py"),
+    ("MODEL.USE_DELTA_FLOW", _WithCfg(lambda v, c: bool(v) and not c.get("VOS", False)),
+     "delta-flow head on a model other than Generalized_VOS_RCNN: only the VOS builder has it, "
+     "lib_vos/vos_modeling/vos_model_builder.py:95-104"),
     # Keypoint R-CNN is built for the FPN family with the v1convX head and the
     # plain per-box decode (engine.KeypointFramePipeline)
     ("KRCNN.NMS_OKS", bool, "OKS NMS of keypoint_results, lib/core/test.py:864-870, as a config "
@@ -317,6 +319,16 @@ def vos_R_101_FPN_3x_gn_dynamic_davis() -> AttrDict:
     return cfg
 
 
+def vos_R_101_FPN_3x_gn_dynamic_delta_flow_davis() -> AttrDict:
+    """The dynamic config with MODEL.USE_DELTA_FLOW: the model makes its own flow
+    from the change of its per-level flow features (vos_model_builder.py:95-104,
+    314-326), no .flo files."""
+    cfg = vos_R_101_FPN_3x_gn_dynamic_davis()
+    cfg.MODEL.USE_DELTA_FLOW = True  # after cfg.VOS = True: rejected on any other model
+    check_supported(cfg)
+    return cfg
+
+
 CONFIGS = {
     "e2e_mask_rcnn_R-50-C4_1x": e2e_mask_rcnn_R_50_C4_1x,
     "e2e_mask_rcnn_R-50-FPN_1x": e2e_mask_rcnn_R_50_FPN_1x,
@@ -325,6 +337,7 @@ CONFIGS = {
     "e2e_keypoint_rcnn_R-50-FPN_1x": e2e_keypoint_rcnn_R_50_FPN_1x,
     "vos_R-101-FPN_3x_gn_static_davis": vos_R_101_FPN_3x_gn_static_davis,
     "vos_R-101-FPN_3x_gn_dynamic_davis": vos_R_101_FPN_3x_gn_dynamic_davis,
+    "vos_R-101-FPN_3x_gn_dynamic_delta_flow_davis": vos_R_101_FPN_3x_gn_dynamic_delta_flow_davis,
 }
 
 

@@ -513,6 +513,31 @@ int vd_flow_to_levels(const float *raw_flow, int F, int H, int W, double im_scal
                                  VD_STREAM(stream));
 }
 
+int vd_delta_flow_features(const VdDeltaFlowLevel *levels, int num_levels, int B, int C,
+                           int layout, const int32_t *valid, void *stream) {
+    if (!levels || num_levels < 1 || num_levels > VD_MAX_LEVELS || !valid) return VD_ERR_ARG;
+    if (layout != VD_LAYOUT_NCHW && layout != VD_LAYOUT_NHWC) return VD_ERR_ARG;
+    DeltaFlowLevels lv = {};
+    for (int l = 0; l < num_levels; ++l) {
+        lv.x[l] = levels[l].features;
+        lv.w[l] = levels[l].weight;
+        lv.feat[l] = levels[l].feat;
+        lv.delta[l] = levels[l].delta;
+        lv.H[l] = levels[l].H;
+        lv.W[l] = levels[l].W;
+    }
+    return launch_delta_flow_features(lv, num_levels, B, C, layout == VD_LAYOUT_NHWC, valid,
+                                      VD_STREAM(stream));
+}
+
+int vd_delta_flow_to_levels(const float *d64, const float *d32, const float *d16, const float *d8,
+                            const float *d4, int B, int Hp, int Wp, float *out64, float *out32,
+                            float *out16, float *out8, float *out4, float *blob, void *stream) {
+    const float *const deltas[5] = {d64, d32, d16, d8, d4};
+    float *const levels[5] = {out64, out32, out16, out8, out4};
+    return launch_delta_flow_to_levels(deltas, B, Hp, Wp, levels, blob, VD_STREAM(stream));
+}
+
 int vd_flow_align_backward(const float *top_grad, const float *features, const float *flow,
                            int B, int C, int H, int W, float *features_grad, float *flow_grad,
                            void *stream) {

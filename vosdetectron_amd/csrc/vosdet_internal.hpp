@@ -189,6 +189,18 @@ struct GnApply {
 // raw .flo-layout flow -> blob-resolution flow + the five FlowAlign level flows (flow_prep.hip)
 int launch_flow_to_levels(const float *raw, int F, int H, int W, double im_scale, int Hr, int Wr,
                           int Hp, int Wp, float *const levels[5], float *blob, hipStream_t s);
+// the delta-flow head (delta_flow.hip): per-level flow features, then the level flows
+struct DeltaFlowLevels {
+    const float *x[5];  // FPN output, B x C x H x W or B x H x W x C
+    const float *w[5];  // packed weight [18][C]: row (ky * 3 + kx) * 2 + o
+    float *feat[5];     // state, B x 2 x H x W, updated in place
+    float *delta[5];    // B x 2 x H x W
+    int H[5], W[5];
+};
+int launch_delta_flow_features(const DeltaFlowLevels &lv, int nlev, int B, int C, int nhwc,
+                               const int32_t *valid, hipStream_t s);
+int launch_delta_flow_to_levels(const float *const deltas[5], int B, int Hp, int Wp,
+                                float *const levels[5], float *blob, hipStream_t s);
 int launch_flow_align_fwd(const float *feat, const float *flow, int B, int C, int H, int W,
                           int nhwc, float *out, hipStream_t s);
 int launch_flow_align_bwd(const float *top_diff, const float *feat, const float *flow, int B,

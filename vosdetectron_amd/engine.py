@@ -711,6 +711,24 @@ def check_flow_args(flow, raw_flow, F, frame_hw, blob_hw, device):
                          "%d; this configuration's is %d x %d" % (ops.FLOW_TILE, Hp, Wp))
 
 
+def check_delta_flow_args(flow, raw_flow, blob_hw):
+    """VOSPipeline with MODEL.USE_DELTA_FLOW: the model makes the flow itself, so
+    flow= and raw_flow= are refused (the reference silently overwrites them), and
+    the blob sides must be multiples of ops.FLOW_TILE.  ValueError names the
+    argument.  Needs no device."""
+    if flow is not None:
+        raise ValueError("VOSPipeline.run: flow was given, but MODEL.USE_DELTA_FLOW is on and "
+                         "the model computes its own flow")
+    if raw_flow is not None:
+        raise ValueError("VOSPipeline.run: raw_flow was given, but MODEL.USE_DELTA_FLOW is on "
+                         "and the model computes its own flow")
+    Hp, Wp = blob_hw
+    if Hp % ops.FLOW_TILE or Wp % ops.FLOW_TILE:
+        raise ValueError("VOSPipeline: MODEL.USE_DELTA_FLOW needs a blob whose sides are "
+                         "multiples of %d; this configuration's is %d x %d"
+                         % (ops.FLOW_TILE, Hp, Wp))
+
+
 class VOSPipeline(FramePipeline):
     """The VOS frame loop (lib_vos/tools/infer_davis_sequential.py:134-149 driving
     Generalized_VOS_RCNN._forward, vos_model_builder.py:289-447) for F sequences
@@ -723,6 +741,12 @@ class VOSPipeline(FramePipeline):
                  det_cap=256, device="cuda"):
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
         self._flow = self._raw_flow = None
+        # MODEL.USE_DELTA_FLOW: the model's own flow; level_flows holds the last
+        # step's five level flows [P6 .. P2] (references, not copies)
+        self.delta_flow = bool(cfg.MODEL.USE_DELTA_FLOW)
+        self.level_flows = None
+        if self.delta_flow:
+            check_delta_flow_args(None, None, (self.Hp, self.Wp))
         # each sequence row's previous-frame result (prev_cls_boxes of the
         # reference loop, train_davis_online.py:591-592), for NMS_SMALL_BOX_IOU
         F = batch
@@ -750,6 +774,8 @@ class VOSPipeline(FramePipeline):
             self.prev_counts[list(rows)] = 0
         if rows is None or set(range(self.prev_counts.shape[0])) <= set(int(r) for r in rows):
             self._unfinalized = False
+        if self.delta_flow:
+            self.model.clean_flow_features(rows)
         hs = self.model.hidden_states
         if rows is None or all(h is None for h in hs):
             self.model.clean_hidden_states()
@@ -816,6 +842,9 @@ class VOSPipeline(FramePipeline):
 
     def backbone(self, frames):
         feats = super().backbone(frames)
+        if self.delta_flow:  # every step: the head's state must advance
+            self.level_flows = self.model.delta_flow(feats)
+            return self.model.temporal_fusion(feats, level_flows=self.level_flows)
         return self.model.temporal_fusion(feats, self._flow, level_flows=self._level_flows())
 
     def _level_flows(self):
@@ -846,6 +875,8 @@ class VOSPipeline(FramePipeline):
                 "VOSPipeline.run: the previous step's result has not been through "
                 "frame_results(); TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU need it as the "
                 "next frame's previous result (lib_vos/tools/vos_test.py:113-118, 845-860)")
+        if self.delta_flow:
+            check_delta_flow_args(flow, raw_flow, (self.Hp, self.Wp))
         check_flow_args(flow, raw_flow, int(frames.shape[0]), (self.H, self.W), (self.Hp, self.Wp),
                         self.device)
         self._flow, self._raw_flow = flow, raw_flow

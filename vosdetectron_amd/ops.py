@@ -1855,6 +1855,115 @@ def flow_to_levels(raw_flow: torch.Tensor, im_scale: float, Hp: int, Wp: int,
     return levels, blob
 
 
+_delta_w_cache: dict = {}
+
+
+def delta_flow_weight_cached(w: torch.Tensor) -> torch.Tensor:
+    """A Conv_Delta_Flows_Features weight [2, C, 3, 3] in vd_delta_flow_features'
+    layout [18, C] (row (ky * 3 + kx) * 2 + o), made once per weight tensor and
+    remade when the tensor changes (as split3_weight_cached)."""
+    key = (w.data_ptr(), w._version, tuple(w.shape))
+    i = id(w)
+    ent = _delta_w_cache.get(i)
+    if ent is not None and ent[0]() is w and ent[1] == key:
+        return ent[2]
+    def _drop(r, i=i):
+        if _delta_w_cache.get(i, (None,))[0] is r:
+            del _delta_w_cache[i]
+    wp = w.detach().permute(2, 3, 0, 1).reshape(18, w.shape[1]).contiguous()
+    _delta_w_cache[i] = (weakref.ref(w, _drop), key, wp)
+    return wp
+
+
+def delta_flow_features(feats: Sequence[torch.Tensor], weights: Sequence[torch.Tensor],
+                        state: Sequence[torch.Tensor], valid: torch.Tensor,
+                        layout: Optional[int] = None):
+    """The delta-flow head's per-level flow features (vos_model_builder.py:314-323)
+    for all levels in one launch (vd_delta_flow_features).  feats[i]: B x C x H_i x W_i
+    (NCHW or channels_last, all the same; layout None = read it off the last, largest map);
+    weights[i]: the level's Conv2d weight [2, C, 3, 3]; state[i]: the previous
+    feature B x 2 x H_i x W_i, updated in place to tanh(conv(feats[i])); valid: B
+    int32 on the device, 0 = the row has no previous feature.  Returns the deltas
+    (new - previous where valid, else 0), one B x 2 x H_i x W_i tensor per level."""
+    n = len(feats)
+    if not 1 <= n <= _lib.VD_MAX_LEVELS:
+        raise ValueError("feats must hold 1 .. %d levels, got %d" % (_lib.VD_MAX_LEVELS, n))
+    if len(weights) != n:
+        raise ValueError("weights must hold one tensor per level (%d), got %d" % (n, len(weights)))
+    if len(state) != n:
+        raise ValueError("state must hold one tensor per level (%d), got %d" % (n, len(state)))
+    lay = _fmt(feats[-1], "feats[-1]") if layout is None else int(layout)
+    if lay not in (_lib.VD_LAYOUT_NCHW, _lib.VD_LAYOUT_NHWC):
+        raise ValueError("layout must be VD_LAYOUT_NCHW or VD_LAYOUT_NHWC, got %r" % (layout,))
+    B, C = int(feats[0].shape[0]), int(feats[0].shape[1])
+    if C % 64 or C > 512:
+        raise ValueError("feats: C must be a multiple of 64 and at most 512, got %d" % C)
+    if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.dtype != torch.int32 \
+            or tuple(valid.shape) != (B,) or not valid.is_contiguous():
+        raise ValueError("valid must be a contiguous int32 device vector of B = %d rows" % B)
+    arr = (_lib.VdDeltaFlowLevel * n)()
+    keep, deltas = [], []
+    for i in range(n):
+        f = feats[i]
+        if f.dim() != 4 or int(f.shape[0]) != B or int(f.shape[1]) != C:
+            raise ValueError("feats[%d] must be %d x %d x H x W, got %s" % (i, B, C,
+                                                                            tuple(f.shape)))
+        f = _like(f, lay, "feats[%d]" % i)
+        H, W = int(f.shape[2]), int(f.shape[3])
+        w = weights[i]
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != (2, C, 3, 3) or not w.is_cuda \
+                or w.dtype != torch.float32:
+            raise ValueError("weights[%d] must be a float32 device tensor [2, %d, 3, 3]" % (i, C))
+        st = state[i]
+        if not isinstance(st, torch.Tensor) or not st.is_cuda or st.dtype != torch.float32 \
+                or tuple(st.shape) != (B, 2, H, W) or not st.is_contiguous():
+            raise ValueError("state[%d] must be a contiguous float32 device tensor %s"
+                             % (i, (B, 2, H, W)))
+        wp = delta_flow_weight_cached(w)
+        d = torch.empty((B, 2, H, W), dtype=torch.float32, device=f.device)
+        arr[i] = _lib.VdDeltaFlowLevel(f.data_ptr(), H, W, wp.data_ptr(), st.data_ptr(),
+                                       d.data_ptr())
+        keep.append((f, wp))
+        deltas.append(d)
+    check(lib().vd_delta_flow_features(arr, n, B, C, lay, valid.data_ptr(), _stream()),
+          "vd_delta_flow_features")
+    return deltas
+
+
+def delta_flow_to_levels(deltas: Sequence[torch.Tensor], Hp: int, Wp: int,
+                         want_blob: bool = False):
+    """The rest of the delta-flow head in one launch (vd_delta_flow_to_levels):
+    deltas [P6 .. P2] (B x 2 x Hp/k x Wp/k, k = 64 .. 4) bilinearly upsampled to the
+    blob, divided by their scales and summed (data_flow, vos_model_builder.py:
+    319-323), then every FlowAlign.conv_flow_downsample.  Returns (levels, blob):
+    levels[i] the flow of FlowAligns[i] (strides 64 .. 4), blob the B x 2 x Hp x Wp
+    data_flow when want_blob, else None (never written)."""
+    Hp, Wp = int(Hp), int(Wp)
+    if Hp < 1 or Wp < 1 or Hp % FLOW_TILE or Wp % FLOW_TILE:
+        raise ValueError("delta_flow_to_levels: the blob %dx%d is not a multiple of %d"
+                         % (Hp, Wp, FLOW_TILE))
+    if len(deltas) != 5:
+        raise ValueError("deltas must hold 5 maps (P6 .. P2), got %d" % len(deltas))
+    B = int(deltas[0].shape[0]) if isinstance(deltas[0], torch.Tensor) and deltas[0].dim() == 4 \
+        else 0
+    ds = []
+    for i, k in enumerate(FLOW_STRIDES[::-1]):
+        d = _need(deltas[i], "deltas[%d]" % i)
+        if tuple(d.shape) != (B, 2, Hp // k, Wp // k) or B < 1:
+            raise ValueError("deltas[%d] must be B x 2 x %d x %d, got %s"
+                             % (i, Hp // k, Wp // k, tuple(d.shape)))
+        ds.append(d)
+    dev = ds[0].device
+    levels = [torch.empty((B, 2, Hp // k, Wp // k), dtype=torch.float32, device=dev)
+              for k in FLOW_STRIDES[::-1]]
+    blob = torch.empty((B, 2, Hp, Wp), dtype=torch.float32, device=dev) if want_blob else None
+    check(lib().vd_delta_flow_to_levels(*[d.data_ptr() for d in ds], B, Hp, Wp,
+                                        *[l.data_ptr() for l in levels],
+                                        blob.data_ptr() if want_blob else None, _stream()),
+          "vd_delta_flow_to_levels")
+    return levels, blob
+
+
 def flow_align_backward(grad_out, features, flow):
     g = _need(grad_out, "grad_out")
     f = _need(features, "features")

@@ -16,6 +16,11 @@ run on PyTorch-ROCm; everything between them is HIP:
     from the modules' conv_flow_downsample over a blob-resolution flow
     (data_flow), or ready-made from the raw .flo flow by one vd_flow_to_levels
     launch (level_flows, ops.flow_to_levels).
+  * MODEL.USE_DELTA_FLOW (vos_model_builder.py:95-104, 314-326): the model makes
+    the flow itself from the change of a two-channel tanh(conv3x3) feature of every
+    FPN level.  delta_flow() runs it as two launches (vd_delta_flow_features,
+    vd_delta_flow_to_levels) on persistent state buffers and returns the five level
+    flows; the blob-resolution data_flow is never formed.
 """
 from __future__ import annotations
 
@@ -128,10 +133,86 @@ class Generalized_VOS_RCNN(Generalized_RCNN):
             self.FlowAligns = nn.ModuleList([FlowAlign(s) for s in self.fpn_scales])
         self.hidden_states = [None] * 5
         self.update_hidden_states = True
+        self.use_delta_flow = bool(cfg.MODEL.USE_DELTA_FLOW)
+        if self.use_delta_flow:
+            if not g.DYNAMIC_MODEL:
+                raise ValueError("MODEL.USE_DELTA_FLOW needs CONVGRU.DYNAMIC_MODEL: fpn_scales "
+                                 "and the FlowAligns exist only on the dynamic model")
+            self.Conv_Delta_Flows_Features = nn.ModuleList([
+                nn.Sequential(nn.Conv2d(dim, 2, 3, 1, 1, bias=False), nn.Tanh())
+                for _ in range(5)])
+            self.flow_features = [None] * 5  # fused=False: the previous features
+            self._flow_cleared = set()       # fused=False: rows whose feature is forgotten
+            self.flow_state = None           # fused: [B,2,H_i,W_i] buffers, never moved
+            self.flow_valid = None           # fused: int32 [B], 1 = the row has a feature
 
     # -- hidden-state management (vos_model_builder.py:258-297) ---------------- #
     def clean_hidden_states(self):
         self.hidden_states = [None] * 5
+
+    def clean_flow_features(self, rows=None):
+        """vos_model_builder.py:271-274: forget the previous flow features (of batch
+        rows `rows` only, when given: the next step's flow of those rows is zero)."""
+        if rows is None:
+            self.flow_features = [None] * 5
+            self._flow_cleared = set()
+            if self.flow_valid is not None:
+                self.flow_valid.zero_()
+            return
+        rows = [int(r) for r in rows]
+        self._flow_cleared |= set(rows)  # such a row's next difference is zero
+        if self.flow_valid is not None:
+            self.flow_valid[rows] = 0
+
+    def delta_flow(self, blob_conv, fused=None):
+        """The delta-flow head on the FPN outputs [P6..P2] before temporal fusion
+        (vos_model_builder.py:314-326).  Runs on every step: the state advances.
+        fused False: the torch composition; returns data_flow, B x 2 x Hp x Wp
+        (Hp = 4 * P2's height), zero where no previous feature exists.
+        fused (the default on the device): two HIP launches on persistent state
+        buffers; returns the five level flows [P6..P2] for temporal_fusion(
+        level_flows=) -- what the FlowAligns' conv_flow_downsample would make of
+        data_flow."""
+        if not self.use_delta_flow:
+            raise ValueError("delta_flow: the model was built without MODEL.USE_DELTA_FLOW")
+        if len(blob_conv) != 5:
+            raise ValueError("delta_flow: blob_conv must hold 5 maps (P6 .. P2), got %d"
+                             % len(blob_conv))
+        if fused is None:
+            fused = blob_conv[0].is_cuda
+        B = blob_conv[0].shape[0]
+        Hp, Wp = 4 * blob_conv[4].shape[2], 4 * blob_conv[4].shape[3]
+        if not fused:
+            cleared = sorted(self._flow_cleared)
+            self._flow_cleared = set()
+            deltas = [None] * 5
+            for i in range(5):
+                feat = self.Conv_Delta_Flows_Features[i](blob_conv[i])
+                if self.flow_features[i] is not None:
+                    d = feat - self.flow_features[i]
+                    if cleared:
+                        d[cleared] = 0
+                    deltas[i] = d
+                self.flow_features[i] = feat
+            data_flow = torch.zeros((B, 2, Hp, Wp), dtype=blob_conv[0].dtype,
+                                    device=blob_conv[0].device)
+            for i in range(5):
+                if deltas[i] is not None:
+                    s = self.fpn_scales[i]
+                    data_flow = data_flow + F.interpolate(
+                        deltas[i], scale_factor=1. / s, mode="bilinear", align_corners=False) / s
+            return data_flow
+        shapes = [(B, 2, f.shape[2], f.shape[3]) for f in blob_conv]
+        if self.flow_state is None or [tuple(s.shape) for s in self.flow_state] != shapes:
+            dev = blob_conv[0].device
+            self.flow_state = [torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes]
+            self.flow_valid = torch.zeros((B,), dtype=torch.int32, device=dev)
+        deltas = ops.delta_flow_features(
+            blob_conv, [m[0].weight for m in self.Conv_Delta_Flows_Features], self.flow_state,
+            self.flow_valid)
+        self.flow_valid.fill_(1)
+        levels, _ = ops.delta_flow_to_levels(deltas, Hp, Wp)
+        return levels
 
     def set_update_hidden_states(self, update=True):
         self.update_hidden_states = update

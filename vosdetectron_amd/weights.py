@@ -183,4 +183,6 @@ def build_model(cfg, seed: int = 0, device="cuda", fold=True, channels_last=Fals
             m.Keypoint_Head.conv_fcn.to(memory_format=torch.channels_last)
         if vos:
             m.ConvGRUs.to(memory_format=torch.channels_last)
+            if hasattr(m, "Conv_Delta_Flows_Features"):
+                m.Conv_Delta_Flows_Features.to(memory_format=torch.channels_last)
     return m, sd
