@@ -137,6 +137,47 @@ def test_winograd4_route_gate():
             os.environ.pop("VOSDET_WINO4", None)
         else:
             os.environ["VOSDET_WINO4"] = old
+    # the recorded decisions (tests/golden/conv3x3_routes.json, tools/gen_goldens.py
+    # conv3x3_routes): the whole shape grid with no switch set, a subsample per switch
+    import itertools
+    import json
+    with open(os.path.join(os.path.dirname(__file__), "golden", "conv3x3_routes.json")) as f:
+        tab = json.load(f)
+    flags = [tuple(fl) for fl in tab["flags"]]
+    route_calls = [(n, ci, co, h, w, mos, w4) for n, (h, w), (ci, co), (mos, w4)
+                   in itertools.product(tab["N"], tab["HW"], tab["C"], flags)]
+    grouped_calls = [(n, ci, co, h, w, g) for n, (h, w), (ci, co), g
+                     in itertools.product(tab["N"], tab["HW"], tab["C"], tab["groups"])]
+    pick_calls = [(n, h, w, allow) for n, (h, w), allow
+                  in itertools.product(tab["N"], tab["HW"], (True, False))]
+    assert len(route_calls) == 5280 and len(tab["sets"]) == 10
+    switches = sorted({k for s in tab["sets"] for k in s["env"]})
+    saved = {k: os.environ.pop(k) for k in switches if k in os.environ}
+    try:
+        for s in tab["sets"]:
+            os.environ.update(s["env"])
+            ri = s["route_idx"] if s["route_idx"] is not None else range(len(route_calls))
+            gi = s["grouped_idx"] if s["grouped_idx"] is not None else range(len(grouped_calls))
+            assert len(ri) == len(s["route"]) and len(gi) == len(s["grouped"])
+            for i, c in zip(ri, s["route"]):
+                got, want = r(*route_calls[i]), tab["route_codes"][c]
+                # `is`: a layout of False (one map per launch) is not 0 and not None
+                assert got[0] == want[0] and (got[1] is want[1] or (
+                    isinstance(want[1], str) and got[1] == want[1])), (s["env"], route_calls[i], got)
+            for i, c in zip(gi, s["grouped"]):
+                got, want = modeling.conv3x3_grouped_route(*grouped_calls[i]), tab["grouped_codes"][c]
+                assert got is want or (isinstance(want, str) and got == want), \
+                    (s["env"], grouped_calls[i], got)
+            for c, want in zip(pick_calls, s["pick_mosaic"]):
+                got = modeling._pick_mosaic(*c)
+                assert (got[0] is want[0] or (isinstance(want[0], str) and got[0] == want[0])) \
+                    and got[1] == want[1], (s["env"], c, got)
+            for k in s["env"]:
+                del os.environ[k]
+    finally:
+        for k in switches:
+            os.environ.pop(k, None)
+        os.environ.update(saved)
     x = torch.randn(1, 64, 50, 84)
     with bench._WinoFlops(frames=32) as wf:
         F.conv2d(x, torch.randn(256, 64, 3, 3), None, 1, 1)  # 32 x 4 x 3 x 4 WGs: F(4x4)

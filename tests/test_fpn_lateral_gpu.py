@@ -96,7 +96,7 @@ def test_fpn_lateral_module_follows_reloaded_weights():
     from vosdetectron_amd import modeling
     m = modeling.TopdownLateral(256, 256).to(DEV)
     modeling.prepare_topdown_lateral(m)
-    assert m._vd_wf is not None  # K = 256: the default fused width
+    assert m.fused_lateral  # K = 256: the default fused width
     lat, w, b, t, ref = _case(2, 256, 40, 56, 11)
     with torch.no_grad():
         m.conv_lateral.weight.copy_(torch.randn_like(w))

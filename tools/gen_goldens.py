@@ -29,6 +29,8 @@ Usage: python tools/gen_goldens.py   (writes tests/golden/*.npz)
        python tools/gen_goldens.py vos_post   (only tests/golden/vos_post.npz)
        python tools/gen_goldens.py soft_nms   (only tests/golden/soft_nms.npz)
        python tools/gen_goldens.py nms_oks    (only tests/golden/nms_oks.npz)
+       python tools/gen_goldens.py conv3x3_routes   (only tests/golden/conv3x3_routes.json:
+                                               this checkout's own route decisions)
 """
 import os
 import sys
@@ -706,8 +708,86 @@ def gen_nms_oks_fixture():
     print("wrote nms_oks.npz: %d bytes" % os.path.getsize(os.path.join(OUT, "nms_oks.npz")))
 
 
+ROUTE_N = (1, 2, 3, 16, 32, 64, 100, 1600, 3200, 6400, 8000)
+ROUTE_HW = ((200, 336), (192, 320), (120, 214), (100, 168), (60, 107), (50, 84), (30, 54),
+            (25, 42), (15, 27), (13, 21), (28, 28), (14, 14), (8, 14), (7, 7), (2, 4))
+ROUTE_C = ((256, 256), (64, 64), (128, 128), (512, 512), (256, 96), (8, 64), (1024, 256),
+           (4104, 64))
+ROUTE_FLAGS = ((True, True), (True, False), (False, True), (False, False))  # mosaic, wino4
+ROUTE_GROUPS = (1, 32, 64)
+ROUTE_ENVS = ({}, {"VOSDET_WINO4": "0"}, {"VOSDET_WINO4_ROWS": "0"},
+              {"VOSDET_WINO4_MOSAIC": "0"}, {"VOSDET_WINO4_OCTET": "0"},
+              {"VOSDET_WINO4_GRID": "0"}, {"VOSDET_WINO4_GROUPED": "0"},
+              {"VOSDET_WINO_MOSAIC": "0"}, {"VOSDET_WINO_MOSAIC": "1"},
+              {"VOSDET_CONV3X3_ALGO": "igemm"})
+
+
+def gen_conv3x3_routes_fixture():
+    """tests/golden/conv3x3_routes.json: what this checkout's own
+    modeling.conv3x3_route / conv3x3_grouped_route / _pick_mosaic answer over a grid of
+    shapes (no reference code involved): the whole grid with no switch set, and every
+    eighth call of it under each VOSDET_* switch that steers a route.  Inputs and
+    results only; test_bench_cpu.test_winograd4_route_gate replays it."""
+    import itertools
+    import json
+    import subprocess
+    from vosdetectron_amd import modeling
+
+    route_calls = [(n, ci, co, h, w, mos, w4) for n, (h, w), (ci, co), (mos, w4)
+                   in itertools.product(ROUTE_N, ROUTE_HW, ROUTE_C, ROUTE_FLAGS)]
+    grouped_calls = [(n, ci, co, h, w, g) for n, (h, w), (ci, co), g
+                     in itertools.product(ROUTE_N, ROUTE_HW, ROUTE_C, ROUTE_GROUPS)]
+    pick_calls = [(n, h, w, allow) for n, (h, w), allow
+                  in itertools.product(ROUTE_N, ROUTE_HW, (True, False))]
+    codes = []  # distinct (algorithm, layout) results; the tables index it
+
+    seen = {}
+
+    def code(r):
+        if repr(r) not in seen:
+            seen[repr(r)] = len(codes)
+            codes.append(list(r))
+        return seen[repr(r)]
+
+    grouped_codes = [None, False, "rows"]
+    saved = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith("VOSDET_")}
+    sets = []
+    try:
+        for env in ROUTE_ENVS:
+            os.environ.update(env)
+            # one call in eight, the offset moving on with each block of eight calls
+            keep = (lambda i: True) if not env else (lambda i: i % 8 == (i // 8) % 8)
+            ri = [i for i in range(len(route_calls)) if keep(i)]
+            gi = [i for i in range(len(grouped_calls)) if keep(i)]
+            sets.append({
+                "env": env, "route_idx": ri if env else None,
+                "route": [code(modeling.conv3x3_route(*route_calls[i])) for i in ri],
+                "grouped_idx": gi if env else None,
+                "grouped": [[c is g for c in grouped_codes].index(True) for g in
+                            (modeling.conv3x3_grouped_route(*grouped_calls[i]) for i in gi)],
+                "pick_mosaic": [list(modeling._pick_mosaic(*c)) for c in pick_calls]})
+            for k in env:
+                del os.environ[k]
+    finally:
+        os.environ.update(saved)
+    commit = subprocess.run(["git", "rev-parse", "HEAD"], cwd=REPO, capture_output=True,
+                            text=True, check=True).stdout.strip()
+    doc = {"generated_at_commit": commit,
+           "N": ROUTE_N, "HW": ROUTE_HW, "C": ROUTE_C, "flags": ROUTE_FLAGS,
+           "groups": ROUTE_GROUPS, "route_codes": codes, "grouped_codes": grouped_codes,
+           "sets": sets}
+    path = os.path.join(OUT, "conv3x3_routes.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+        f.write("\n")
+    print("wrote conv3x3_routes.json: %d bytes, %d route results" % (
+        os.path.getsize(path), len(codes)))
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["vos_post"]:
+    if sys.argv[1:] == ["conv3x3_routes"]:
+        gen_conv3x3_routes_fixture()
+    elif sys.argv[1:] == ["vos_post"]:
         gen_vos_post_fixture()
     elif sys.argv[1:] == ["soft_nms"]:
         gen_soft_nms_fixture()

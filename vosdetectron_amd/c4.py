@@ -28,8 +28,8 @@ import torch.nn.functional as F
 from . import ops
 from .engine import FramePipeline
 from .modeling import (Bottleneck, FastRCNNOutputs, Generalized_RCNN, MaskRCNNOutputs,
-                       ResNetBody, _conv_epi, generate_anchors, prepare_bottlenecks,
-                       prepare_resnet_body)
+                       ResNetBody, _conv_epi, _prepared, generate_anchors,
+                       prepare_bottlenecks, prepare_resnet_body)
 
 
 def _conv4_counts(conv_body: str):
@@ -142,19 +142,16 @@ class MaskHeadV0upshare(nn.Module):
         [R H W, 2048] x [2048, 2 x 2 x 256] with the bias + ReLU epilogue (the split-bf16
         kernel; MIOpen's transposed conv took 3.6 ms per 16-frame step), then the
         depth-to-space shuffle; None where no GEMM serves the shape."""
-        w = self.upconv5.weight  # Cin x Cout x 2 x 2
-        key = (w.data_ptr(), w._version)
-        if getattr(self, "_vd_up_key", None) != key:
-            self._vd_up_wt = w.detach().permute(2, 3, 1, 0).reshape(4 * w.shape[1],
-                                                                    w.shape[0]).contiguous()
-            self._vd_up_b = self.upconv5.bias.detach().repeat(4).contiguous()
-            self._vd_up_key = key
+        w, b = self.upconv5.weight, self.upconv5.bias  # w: Cin x Cout x 2 x 2
+        up_wt, up_b = _prepared(self, "_vd_up", (w, b), lambda: (
+            w.detach().permute(2, 3, 1, 0).reshape(4 * w.shape[1], w.shape[0]).contiguous(),
+            b.detach().repeat(4).contiguous()))
         R, C, H, W = h.shape
-        y = ops.gemm_bias_act(h.permute(0, 2, 3, 1).reshape(R * H * W, C), self._vd_up_wt,
-                              self._vd_up_b, relu=True)
+        y = ops.gemm_bias_act(h.permute(0, 2, 3, 1).reshape(R * H * W, C), up_wt, up_b,
+                              relu=True)
         if y is None:
             return None
-        co = self._vd_up_wt.shape[0] // 4
+        co = up_wt.shape[0] // 4
         y = y.view(R, H, W, 2, 2, co).permute(0, 1, 3, 2, 4, 5).reshape(R, 2 * H, 2 * W, co)
         return y.permute(0, 3, 1, 2)
 

@@ -138,9 +138,7 @@ def _wino4_mode(N: int, Cin: int, Cout: int, H: int, W: int):
     VOSDET_WINO4=0 turns F(4x4) off."""
     if os.environ.get("VOSDET_WINO4", "1") == "0":
         return None
-    if Cout % 64 or Cin % 8 or Cout == 0 or Cin == 0 or Cin > ops.WINO_MAX_CIN:
-        return None
-    if H * W * Cin >= (1 << 31):
+    if not ops.wino_serves(Cin, Cout) or H * W * Cin >= (1 << 31):
         return None
     use = _wino4_block_use(H, W)
     wgs = N * -(-H // 16) * -(-W // 32) * (Cout // 64)
@@ -159,11 +157,6 @@ def _wino4_mode(N: int, Cin: int, Cout: int, H: int, W: int):
     return False if plain else None
 
 
-def _wino4_ok(N: int, Cin: int, Cout: int, H: int, W: int) -> bool:
-    """conv3x3_route's F(4x4) gate (VOSDET_WINO4=0 turns it off)."""
-    return _wino4_mode(N, Cin, Cout, H, W) is not None
-
-
 def _wino4_pair_ok(N: int, Cin: int, Cout: int, H: int, W: int) -> bool:
     """F(4x4) over small maps two per 16 x 32 block (vd_conv3x3_wino4_mosaic_bias_act;
     the mask head's 14 x 14 RoI maps: 77 % of each block real output; 2.43 vs 2.87 ms
@@ -173,7 +166,7 @@ def _wino4_pair_ok(N: int, Cin: int, Cout: int, H: int, W: int) -> bool:
     turns both off."""
     if os.environ.get("VOSDET_WINO4_MOSAIC", "1") == "0" or os.environ.get("VOSDET_WINO4", "1") == "0":
         return False
-    if Cout % 64 or Cin % 8 or Cout == 0 or Cin == 0 or Cin > ops.WINO_MAX_CIN:
+    if not ops.wino_serves(Cin, Cout):
         return False
     cell, per = (8, 8) if (H <= 7 and W <= 7) else (16, 2)  # octets / pairs per block
     if cell == 8 and os.environ.get("VOSDET_WINO4_OCTET", "1") == "0":
@@ -204,16 +197,16 @@ def _wino4_grid_better(N: int, Cin: int, H: int, W: int) -> bool:
 def conv3x3_route(N: int, Cin: int, Cout: int, H: int, W: int, mosaic=True, wino4=True):
     """(algorithm, mosaic) the engine runs a 3x3 / stride-1 / pad-1 fp32 conv of an
     N x Cin x H x W channels_last batch with: ('wino4', None) -- Winograd F(4x4,3x3),
-    csrc/conv3x3_wino4.hip, where _wino4_ok holds -- else ('wino', layout) -- Winograd
-    F(2x2,3x3), csrc/conv3x3_wino.hip, from 2^12 output pixels where its blocks are
+    csrc/conv3x3_wino4.hip, where _wino4_mode or _wino4_pair_ok holds -- else
+    ('wino', layout) -- Winograd F(2x2,3x3), csrc/conv3x3_wino.hip, from 2^12 output pixels where its blocks are
     >= 60 % real output (Cout % 64, Cin % 8) -- else ('igemm', None), the implicit
     GEMM (csrc/conv3x3.hip), from 2^18 pixels, else (None, None): MIOpen / CK.
     One rule for the engine (_conv3x3_mfma) and the bench's executed-FLOP count.
     wino4=False leaves F(4x4) out (the keypoint head: its accuracy bound)."""
     npx = N * H * W
     mos, use = _pick_mosaic(N, H, W, mosaic)
-    wino = (os.environ.get("VOSDET_CONV3X3_ALGO", CONV3X3_ALGO) == "wino" and Cout % 64 == 0
-            and Cin % 8 == 0 and Cout > 0 and Cin <= ops.WINO_MAX_CIN)
+    wino = (os.environ.get("VOSDET_CONV3X3_ALGO", CONV3X3_ALGO) == "wino"
+            and ops.wino_serves(Cin, Cout))
     w4 = _wino4_mode(N, Cin, Cout, H, W) if wino and wino4 else None
     if w4 is not None:
         return "wino4", (w4 or None)
@@ -253,23 +246,96 @@ def _count_route(name: str):
     ROUTE_COUNTS[name] = ROUTE_COUNTS.get(name, 0) + 1
 
 
-def _dilated2_ok(conv: nn.Conv2d, x) -> bool:
-    """A 3x3 / dilation-2 / pad-2 conv (the VOS mask head, MRCNN.DILATION = 2) of
-    even-sized channels_last maps, which _conv3x3_mfma runs as the plain 3x3 conv of
-    its four polyphase sub-maps (VOSDET_WINO_DILATED=0 keeps MIOpen)."""
-    return (conv.dilation == (2, 2) and conv.padding == (2, 2) and conv.stride == (1, 1)
-            and conv.kernel_size == (3, 3) and conv.groups == 1 and x.dim() == 4
-            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.is_cuda
-            and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
-            and os.environ.get("VOSDET_WINO_DILATED", "1") != "0"
-            and os.environ.get("VOSDET_CONV3X3_MFMA", "1") != "0")
+def _prepared(owner, slot: str, sources, make, *extra):
+    """make(), kept on `owner` as attribute `slot` and remade when a tensor of `sources`
+    changes -- its storage, version counter or shape: an in-place update, a
+    load_state_dict -- or a value of `extra` does.  The one cache of everything derived
+    from a live weight (transformed 3x3 weights, packed stems, 2-D views, concatenations)."""
+    key = tuple((t.data_ptr(), t._version, t.shape) for t in sources) + extra
+    ent = getattr(owner, slot, None)
+    if ent is None or ent[0] != key:
+        ent = (key, make())
+        setattr(owner, slot, ent)
+    return ent[1]
+
+
+def _conv3x3_kind(conv: nn.Conv2d, x):
+    """How the hand-written kernels can serve `conv` on x -- a 3x3 / stride-1 conv of a
+    channels_last fp32 device tensor, VOSDET_CONV3X3_MFMA not 0: "dense" or "grouped"
+    (pad 1), "dilated2" (dilation 2 / pad 2, the VOS mask head's MRCNN.DILATION = 2, on
+    even-sized maps; VOSDET_WINO_DILATED=0 keeps MIOpen), or None: not served."""
+    if (os.environ.get("VOSDET_CONV3X3_MFMA", "1") == "0" or conv.kernel_size != (3, 3)
+            or conv.stride != (1, 1) or x.dim() != 4 or not x.is_cuda
+            or x.dtype != torch.float32
+            or not x.is_contiguous(memory_format=torch.channels_last)):
+        return None
+    if conv.padding == (1, 1) and conv.dilation == (1, 1):
+        return "grouped" if conv.groups > 1 else "dense"
+    if (conv.padding == (2, 2) and conv.dilation == (2, 2) and conv.groups == 1
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+            and os.environ.get("VOSDET_WINO_DILATED", "1") != "0"):
+        return "dilated2"
+    return None
+
+
+def _conv3x3_attempts(kind, N, Cin, Cout, H, W, groups, mosaic, wino4):
+    """The (algorithm, layout) pairs _conv3x3_mfma tries on a conv of `kind`, in order,
+    until a kernel returns an output (each returns None for a shape it does not serve);
+    after the last, MIOpen.  N, H, W: of the maps the kernels see (a dilation-2 conv's
+    4N polyphase sub-maps)."""
+    if kind == "grouped":  # only F(4x4) has a grouped form
+        mode = conv3x3_grouped_route(N, Cin, Cout, H, W, groups)
+        if mode is not None:
+            yield "wino4_grouped", mode
+        return
+    algo, lay = conv3x3_route(N, Cin, Cout, H, W, mosaic, wino4)
+    if algo == "wino4":
+        if (kind == "dilated2" and lay in ("pair", "grid", None)
+                and os.environ.get("VOSDET_DILATED_INPLACE", "1") != "0"):
+            # the kernel reads / writes the sub-maps in place: no polyphase copies
+            yield "dilated2", lay
+        yield "wino4", lay
+        algo, lay = "wino", _pick_mosaic(N, H, W, mosaic)[0]
+    if algo == "wino":
+        yield "wino", lay
+        algo, lay = ("igemm" if N * H * W >= _CONV3X3_MIN_PIXELS else None), None
+    if algo == "igemm":
+        yield "igemm", None
+
+
+# ROUTE_COUNTS' name of an (algorithm, layout) attempt; any other pair: the algorithm's
+_ROUTE_NAMES = {("wino4", "rows"): "wino4_rows", ("wino4", "pair"): "wino4_pair",
+                ("wino4", "grid"): "wino4_grid", ("wino", True): "wino_rows",
+                ("wino", "2d"): "wino_2d"}
+
+
+def _conv3x3_launch(conv: nn.Conv2d, algo, lay, x, b, relu):
+    """One attempt: `algo`'s kernel on x with its weight operand, transformed once per
+    live weight (_prepared)."""
+    w = conv.weight
+    if algo == "wino4_grouped":
+        u = _prepared(conv, "_vd_u4g", (w,),
+                      lambda: ops.conv3x3_wino4_grouped_weight(w.detach(), conv.groups))
+        return ops.conv3x3_wino4_bias_act(x, u, b, relu=relu, mosaic=lay or False,
+                                          groups=conv.groups)
+    if algo in ("wino4", "dilated2"):
+        u = _prepared(conv, "_vd_u4", (w,), lambda: ops.conv3x3_wino4_weight(w.detach()))
+        if algo == "dilated2":
+            return ops.conv3x3_wino4_dilated2_bias_act(x, u, b, relu=relu, layout=lay or False)
+        return ops.conv3x3_wino4_bias_act(x, u, b, relu=relu, mosaic=lay or False)
+    if algo == "wino":
+        u = _prepared(conv, "_vd_u", (w,), lambda: ops.conv3x3_wino_weight(w.detach()))
+        return ops.conv3x3_wino_bias_act(x, u, b, relu=relu, mosaic=lay)
+    w2 = _prepared(conv, "_vd_w2", (w,), lambda: ops.conv3x3_weight(w.detach()))
+    return ops.conv3x3_bias_act(x, w2, b, relu=relu)
 
 
 def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True, wino4=True):
     """conv (3x3, stride 1, pad 1) of a channels_last fp32 tensor on the
     hand-written MFMA kernels with the bias (+ ReLU) epilogue, or None where
-    they do not apply (other geometry, VOSDET_CONV3X3_MFMA=0).  The algorithm
-    is conv3x3_route's.  mosaic=True lets Winograd run the batch as a mosaic of
+    they do not apply (_conv3x3_kind: other geometry, VOSDET_CONV3X3_MFMA=0).  The
+    algorithm is conv3x3_route's, the order of fallbacks _conv3x3_attempts'.
+    mosaic=True lets Winograd run the batch as a mosaic of
     maps with per-map zero padding (_pick_mosaic): the mask head's 14 x 14 RoI
     maps 8 side by side per 112-column row -- every 8 x 16-pixel block real
     output (77 % one map per block, 87.5 % stacked in one column) -- and the
@@ -280,102 +346,32 @@ def _conv3x3_mfma(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True, wino4=
     sub-map's neighbours and its zero padding is one sub-pixel: space-to-batch, the
     same kernels on 4N maps of H/2 x W/2 (the VOS mask head's 14 x 14 RoI maps become
     7 x 7 octets), batch-to-space."""
-    if _dilated2_ok(conv, x):
-        N, C, H, W = x.shape
-        algo, mos = conv3x3_route(4 * N, C, conv.weight.shape[0], H // 2, W // 2, mosaic,
-                                  wino4)
-        if (algo == "wino4" and mos in ("pair", "grid", None)
-                and os.environ.get("VOSDET_DILATED_INPLACE", "1") != "0"):
-            # the kernel reads / writes the sub-maps in place: no polyphase copies
-            w = conv.weight
-            key = (w.data_ptr(), w._version)
-            if getattr(conv, "_vd_u4_key", None) != key:
-                conv._vd_u4 = ops.conv3x3_wino4_weight(w.detach())
-                conv._vd_u4_key = key
-            b = conv.bias.detach() if (bias and conv.bias is not None) else None
-            y = ops.conv3x3_wino4_dilated2_bias_act(x, conv._vd_u4, b, relu=relu,
-                                                    layout=mos or False)
-            if y is not None:
-                _count_route("dilated2")
-                return y
-        xs = x.permute(0, 2, 3, 1).reshape(N, H // 2, 2, W // 2, 2, C).permute(
-            2, 4, 0, 1, 3, 5).reshape(4 * N, H // 2, W // 2, C).permute(0, 3, 1, 2)
-        y = _conv3x3_mfma_core(conv, xs, bias, relu, mosaic, as_plain=True, wino4=wino4)
-        if y is None:
-            return None
-        Co = y.shape[1]
-        y = y.permute(0, 2, 3, 1).reshape(2, 2, N, H // 2, W // 2, Co).permute(
-            2, 3, 0, 4, 1, 5).reshape(N, H, W, Co).permute(0, 3, 1, 2)
-        _count_route("dilated2")
-        return y
-    return _conv3x3_mfma_core(conv, x, bias, relu, mosaic, wino4=wino4)
-
-
-def _conv3x3_mfma_core(conv: nn.Conv2d, x, bias=True, relu=False, mosaic=True,
-                       as_plain=False, wino4=True):
-    """_conv3x3_mfma's body; as_plain: a dilation-2 / pad-2 conv taken as the pad-1 conv
-    it is on polyphase sub-maps (the caller has split x)."""
-    dil = (1, 1) if as_plain else conv.dilation
-    pad = (1, 1) if as_plain else conv.padding
-    if (conv.groups > 1 and os.environ.get("VOSDET_CONV3X3_MFMA", "1") != "0" and x.is_cuda
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and pad == (1, 1)
-            and dil == (1, 1) and x.dtype == torch.float32
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        mode = conv3x3_grouped_route(x.shape[0], x.shape[1], conv.weight.shape[0], x.shape[2],
-                                     x.shape[3], conv.groups)
-        if mode is not None:
-            w = conv.weight
-            key = (w.data_ptr(), w._version)
-            if getattr(conv, "_vd_u4g_key", None) != key:
-                conv._vd_u4g = ops.conv3x3_wino4_grouped_weight(w.detach(), conv.groups)
-                conv._vd_u4g_key = key
-            b = conv.bias.detach() if (bias and conv.bias is not None) else None
-            if conv._vd_u4g is not None:
-                y = ops.conv3x3_wino4_bias_act(x, conv._vd_u4g, b, relu=relu,
-                                               mosaic=mode or False, groups=conv.groups)
-                if y is not None:
-                    _count_route("wino4_grouped")
-                    return y
-    if (os.environ.get("VOSDET_CONV3X3_MFMA", "1") == "0" or not x.is_cuda
-            or conv.kernel_size != (3, 3) or conv.stride != (1, 1) or pad != (1, 1)
-            or dil != (1, 1) or conv.groups != 1 or x.dtype != torch.float32
-            or not x.is_contiguous(memory_format=torch.channels_last)):
+    kind = _conv3x3_kind(conv, x)
+    if kind is None:
         if conv.kernel_size == (3, 3):
             _count_route("miopen")
         return None
-    w = conv.weight
-    key = (w.data_ptr(), w._version)
     b = conv.bias.detach() if (bias and conv.bias is not None) else None
-    algo, mos = conv3x3_route(x.shape[0], x.shape[1], w.shape[0], x.shape[2], x.shape[3],
-                              mosaic, wino4)
-    if algo == "wino4":
-        if getattr(conv, "_vd_u4_key", None) != key:
-            conv._vd_u4 = ops.conv3x3_wino4_weight(w.detach())
-            conv._vd_u4_key = key
-        y = ops.conv3x3_wino4_bias_act(x, conv._vd_u4, b, relu=relu, mosaic=mos or False)
-        if y is not None:
-            _count_route({"pair": "wino4_pair", "rows": "wino4_rows",
-                          "grid": "wino4_grid"}.get(mos, "wino4"))
-            return y
-        algo, mos = "wino", _pick_mosaic(x.shape[0], x.shape[2], x.shape[3], mosaic)[0]
-    if algo == "wino":
-        if getattr(conv, "_vd_u_key", None) != key:
-            conv._vd_u = ops.conv3x3_wino_weight(w.detach())
-            conv._vd_u_key = key
-        y = ops.conv3x3_wino_bias_act(x, conv._vd_u, b, relu=relu, mosaic=mos)
-        if y is not None:
-            _count_route({False: "wino", True: "wino_rows", "2d": "wino_2d"}[mos])
-            return y
-        algo = "igemm" if x.shape[0] * x.shape[2] * x.shape[3] >= _CONV3X3_MIN_PIXELS else None
-    if algo is None:
-        _count_route("miopen")
-        return None
-    if getattr(conv, "_vd_w2_key", None) != key:
-        conv._vd_w2 = ops.conv3x3_weight(w.detach())
-        conv._vd_w2_key = key
-    y = ops.conv3x3_bias_act(x, conv._vd_w2, b, relu=relu)
-    _count_route("igemm" if y is not None else "miopen")
-    return y
+    N, C, H, W = x.shape
+    # the maps the kernels see
+    sn, sh, sw = (4 * N, H // 2, W // 2) if kind == "dilated2" else (N, H, W)
+    xs = x
+    for algo, lay in _conv3x3_attempts(kind, sn, C, conv.weight.shape[0], sh, sw, conv.groups,
+                                       mosaic, wino4):
+        if kind == "dilated2" and algo != "dilated2" and xs is x:  # space-to-batch
+            xs = x.permute(0, 2, 3, 1).reshape(N, sh, 2, sw, 2, C).permute(
+                2, 4, 0, 1, 3, 5).reshape(sn, sh, sw, C).permute(0, 3, 1, 2)
+        y = _conv3x3_launch(conv, algo, lay, xs, b, relu)
+        if y is None:
+            continue
+        _count_route(_ROUTE_NAMES.get((algo, lay), algo))
+        if xs is not x:  # batch-to-space
+            y = y.permute(0, 2, 3, 1).reshape(2, 2, N, sh, sw, y.shape[1]).permute(
+                2, 3, 0, 4, 1, 5).reshape(N, H, W, y.shape[1]).permute(0, 3, 1, 2)
+            _count_route("dilated2")
+        return y
+    _count_route("miopen")
+    return None
 
 
 CONV3X3_ALGO = "wino"  # the 3x3 algorithm the engine uses (VOSDET_CONV3X3_ALGO overrides)
@@ -522,7 +518,6 @@ def _gemm_conv1x1_s2(x, w2d, bias, relu=True, res=None):
 def _gemm_ok(x) -> bool:
     """GEMM epilogue path: channels_last fp32 activations (VOSDET_GEMM_EPILOGUE=0
     switches it off for A/B measurements)."""
-    import os
     return (os.environ.get("VOSDET_GEMM_EPILOGUE", "1") != "0" and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
             and x.dtype == torch.float32)
@@ -538,7 +533,6 @@ def _conv2_prologue_ok(conv2: nn.Conv2d, w3) -> bool:
     applies as it loads its input (ops.gemm_split3_bias_act a_bias), instead of a
     separate pass: conv3 must take the split GEMM (K = conv2's channels >= SPLIT3_MIN_K,
     K % 16, N % 64).  VOSDET_CONV2_PROLOGUE=0 keeps the separate pass."""
-    import os
     k = conv2.out_channels
     return (conv2.groups > 1 and conv2.bias is not None and ops.split3_enabled()
             and k >= ops.SPLIT3_MIN_K and k % 16 == 0 and w3.shape[0] % 64 == 0
@@ -589,18 +583,16 @@ def _gn_conv1x1(conv: nn.Conv2d, x):
             or not ops.split3_enabled()):
         return None
     w = conv.weight
-    if getattr(conv, "_vd_gn_src", None) is not w:
-        conv._vd_gn_w2d = w.detach().reshape(w.shape[0], -1)
-        conv._vd_gn_zb = torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
-        conv._vd_gn_src = w
-    w2d = conv._vd_gn_w2d
+    w2d, zb = _prepared(conv, "_vd_gn", (w,), lambda: (
+        w.detach().reshape(w.shape[0], -1),
+        torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)))
     K, N = w2d.shape[1], w2d.shape[0]
     if K < ops.SPLIT3_MIN_K or K % 16 or N % 64 or x.shape[1] != K:
         return None
     if conv.stride == (1, 1):
-        return _gemm_conv1x1(x, w2d, conv._vd_gn_zb, relu=False)
+        return _gemm_conv1x1(x, w2d, zb, relu=False)
     if conv.stride == (2, 2) and _split3_s2_ok(x, w2d):
-        return _gemm_conv1x1_s2(x, w2d, conv._vd_gn_zb, relu=False)
+        return _gemm_conv1x1_s2(x, w2d, zb, relu=False)
     return None
 
 
@@ -703,11 +695,10 @@ class _StemEpilogue(nn.Module):
         if x.is_cuda:
             if self._fused_ok(x):  # conv + bias + ReLU + max-pool in one MFMA kernel
                 split = os.environ.get("VOSDET_STEM", "split") == "split"
-                key = (self.conv1.weight.data_ptr(), self.conv1.weight._version, split)
-                if getattr(self, "_stem_key", None) != key:
-                    self._stem_packed = ops.stem_pack(self.conv1.weight, split=split)
-                    self._stem_key = key
-                return ops.stem_conv_pool(x, self._stem_packed, self.conv1.bias)
+                w = self.conv1.weight
+                packed = _prepared(self, "_vd_stem", (w,), lambda: ops.stem_pack(w, split=split),
+                                   split)
+                return ops.stem_conv_pool(x, packed, self.conv1.bias)
             h = _conv_nb(self.conv1, x)
             if (h.is_contiguous(memory_format=torch.channels_last) and not h.is_contiguous()
                     and h.shape[1] % 4 == 0 and os.environ.get("VOSDET_STEM_FUSED", "1") != "0"):
@@ -767,6 +758,7 @@ class TopdownLateral(nn.Module):
         else:
             self.conv_lateral = nn.Conv2d(dim_lateral, dim_top, 1, 1, 0)
         self.epilogue = False
+        self.fused_lateral = False  # prepare_topdown_lateral: ops.fpn_lateral_topdown serves it
 
     def forward(self, top, lateral):
         if self.epilogue and lateral.is_cuda:
@@ -774,10 +766,9 @@ class TopdownLateral(nn.Module):
                 return _gn_epi(self.conv_lateral[0], self.conv_lateral[1], lateral, act=None,
                                res=top, up=True)
             c = self.conv_lateral
-            w2d = getattr(self, "_vd_w2d", None)
-            if w2d is None or w2d.data_ptr() != c.weight.data_ptr():
-                # one persistent 2-D view of the weight (ops caches its split image)
-                w2d = self._vd_w2d = c.weight.reshape(c.out_channels, -1)
+            # one persistent 2-D view of the weight (ops caches its split image)
+            w2d = _prepared(self, "_vd_w2d", (c.weight,),
+                            lambda: c.weight.reshape(c.out_channels, -1))
             if ops.split3_enabled() and c.in_channels >= ops.SPLIT3_MIN_K and \
                     c.out_channels % 64 == 0 and c.bias is not None and _is_1x1(c) and \
                     c.stride == (1, 1) and _gemm_ok(lateral) and top.is_cuda and \
@@ -793,15 +784,12 @@ class TopdownLateral(nn.Module):
                                                  residual=_nhwc2d(t), relu=False, up_hw=(H, W))
                     _count_route("fpn_lateral_split3")
                     return y.view(n, H, W, -1).permute(0, 3, 1, 2)
-            wf = getattr(self, "_vd_wf", None)
-            if wf is not None:
+            wf = None
+            if self.fused_lateral:
                 # the packed weight follows the live one (a load_state_dict after
-                # prepare_fpn_body), as the Winograd routes' U keys do
-                w = c.weight
-                key = (w.data_ptr(), w._version)
-                if self._vd_wf_key != key:
-                    wf = self._vd_wf = ops.fpn_lateral_weight(w.detach())
-                    self._vd_wf_key = key
+                # prepare_fpn_body), as the Winograd routes' U does
+                wf = _prepared(self, "_vd_wf", (c.weight,),
+                               lambda: ops.fpn_lateral_weight(c.weight.detach()))
             if wf is not None and _gemm_ok(lateral) and top.shape[2] * 2 == lateral.shape[2] \
                     and top.shape[3] * 2 == lateral.shape[3]:
                 # the lateral 1x1, its bias and the nearest-2x top-down add in one
@@ -857,10 +845,9 @@ class FPNBody(nn.Module):
             # one persistent 2-D view of the weight (the split-bf16 image is cached per
             # tensor object; a fresh view per call would re-split it every step)
             cw = self.conv_top.weight
-            if getattr(self, "_vd_top_src", None) is not cw:
-                self._vd_top_w2d = cw.reshape(self.conv_top.out_channels, -1)
-                self._vd_top_src = cw
-            inner = [_gemm_conv1x1(c[-1], self._vd_top_w2d, self.conv_top.bias, relu=False)]
+            w2d = _prepared(self, "_vd_top_w2d", (cw,),
+                            lambda: cw.reshape(self.conv_top.out_channels, -1))
+            inner = [_gemm_conv1x1(c[-1], w2d, self.conv_top.bias, relu=False)]
         else:
             inner = [self.conv_top(c[-1])]
         for i in range(3):
@@ -1058,16 +1045,16 @@ class FastRCNNOutputs(nn.Module):
     def _cat_weights(self):
         ws = (self.cls_score.weight, self.bbox_pred.weight, self.cls_score.bias,
               self.bbox_pred.bias)
-        key = tuple((t.data_ptr(), t._version) for t in ws)
-        if getattr(self, "_vd_cat_key", None) != key:
+
+        def cat():
             n = ws[0].shape[0] + ws[1].shape[0]
             npad = (n + 63) // 64 * 64
             w = torch.zeros((npad, ws[0].shape[1]), dtype=ws[0].dtype, device=ws[0].device)
             b = torch.zeros((npad,), dtype=ws[0].dtype, device=ws[0].device)
             w[:n] = torch.cat([ws[0], ws[1]])
             b[:n] = torch.cat([ws[2], ws[3]])
-            self._vd_cat, self._vd_cat_key = (w, b), key
-        return self._vd_cat
+            return w, b
+        return _prepared(self, "_vd_cat", ws, cat)
 
     def per_class_deltas(self, bbox_pred, num_classes):
         """vos_test.py:179-190 decodes the fg deltas once and tiles the boxes over
@@ -1502,14 +1489,13 @@ def _fpn_lateral_fused_k():
 
 
 def prepare_topdown_lateral(m: TopdownLateral, epilogue: bool = True):
-    """One top-down lateral module: the fused-lateral weight (fragment order, keyed
-    by the live weight so a later load_state_dict repacks it) and the epilogue flag."""
-    m._vd_wf = m._vd_wf_key = None
+    """One top-down lateral module: whether the fused lateral launch serves it (its
+    weight, in fragment order, is packed on first use and follows the live one) and the
+    epilogue flag."""
     c = m.conv_lateral
-    if epilogue and not m.use_gn and c.weight.is_cuda and _is_1x1(c) and c.stride == (1, 1) \
-            and c.bias is not None and c.in_channels in _fpn_lateral_fused_k():
-        m._vd_wf = ops.fpn_lateral_weight(c.weight.detach())
-        m._vd_wf_key = (c.weight.data_ptr(), c.weight._version)
+    m.fused_lateral = bool(
+        epilogue and not m.use_gn and c.weight.is_cuda and _is_1x1(c) and c.stride == (1, 1)
+        and c.bias is not None and c.in_channels in _fpn_lateral_fused_k())
     m.epilogue = epilogue
 
 

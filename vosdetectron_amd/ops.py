@@ -542,8 +542,9 @@ def gemm_plan_list() -> list:
 # below it the GEMMs are HBM-bound and the fp32 kernels are as fast
 # (profiles/r06/gemm_split3/)
 SPLIT3_MIN_K = 128
-# id(weight tensor) -> (weakref to it, key, split image); an entry leaves with its tensor
-_split3_cache = {}
+# (transform, id(weight tensor)) -> (weakref to it, key, transformed weight); an entry
+# leaves with its tensor
+_weight_cache = {}
 
 
 def split3_enabled() -> bool:
@@ -551,26 +552,32 @@ def split3_enabled() -> bool:
     return os.environ.get("VOSDET_GEMM_SPLIT3", "1") != "0"
 
 
-def split3_weight_cached(w: torch.Tensor) -> Optional[torch.Tensor]:
-    """gemm_split3_weight(w), made once per weight tensor and remade when the tensor
-    changes (its storage or version counter: an in-place update, load_state_dict)."""
+def _weight_cached(w: torch.Tensor, transform, trace: Optional[str] = None):
+    """transform(w), made once per weight tensor object (callers such as gemm_bias_act
+    hold a bare weight, no module to keep it on) and remade when the tensor changes (its
+    storage, version counter or shape: an in-place update, load_state_dict)."""
     key = (w.data_ptr(), w._version, tuple(w.shape))
-    i = id(w)
-    ent = _split3_cache.get(i)
+    slot = (transform, id(w))
+    ent = _weight_cache.get(slot)
     if ent is not None and ent[0]() is w and ent[1] == key:
         return ent[2]
-    def _drop(r, i=i):
-        if _split3_cache.get(i, (None,))[0] is r:
-            del _split3_cache[i]
+    def _drop(r, slot=slot):
+        if _weight_cache.get(slot, (None,))[0] is r:
+            del _weight_cache[slot]
     ref = weakref.ref(w, _drop)
-    if os.environ.get("VOSDET_SPLIT3_TRACE") == "1":  # research: report every (re)split
+    if trace is not None and os.environ.get(trace) == "1":  # research: report every remake
         import traceback
-        sys.stderr.write("split3 weight %s (cache %s)\n%s" % (
-            tuple(w.shape), "stale" if ent is not None else "miss",
-            "".join(traceback.format_stack(limit=6)[:-1])))
-    wp = gemm_split3_weight(w)
-    _split3_cache[i] = (ref, key, wp)
+        sys.stderr.write("%s %s (cache %s)\n%s" % (
+            transform.__name__, tuple(w.shape), "stale" if ent is not None else "miss",
+            "".join(traceback.format_stack(limit=7)[:-2])))
+    wp = transform(w)
+    _weight_cache[slot] = (ref, key, wp)
     return wp
+
+
+def split3_weight_cached(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """gemm_split3_weight(w) through _weight_cached (VOSDET_SPLIT3_TRACE=1 reports each)."""
+    return _weight_cached(w, gemm_split3_weight, "VOSDET_SPLIT3_TRACE")
 
 
 def gemm_bias_act(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
@@ -738,38 +745,67 @@ def conv3x3_weight(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 2, 3, 1).contiguous()
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _conv3x3_x(x: torch.Tensor):
+    """The conv3x3_*_bias_act entries' check of x; its (N, C, H, W)."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 \
+            or not x.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("x must be a channels_last fp32 device tensor")
+    return x.shape
+
+
+def _conv3x3_bias_out(x: torch.Tensor, bias, Cout: int, out):
+    """The rest of those entries' preamble, once the weight operand has given Cout:
+    (the bias as _need gives it or None, `out` -- allocated, or checked where given)."""
+    b_ = _need(bias, "bias") if bias is not None else None
+    if b_ is not None and b_.numel() != Cout:
+        raise ValueError("bias must have %d elements" % Cout)
+    shape = (x.shape[0], Cout, x.shape[2], x.shape[3])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device,
+                          memory_format=torch.channels_last)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device \
+            or not out.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("out must be a channels_last fp32 %s tensor on x's device" % (shape,))
+    return b_, out
+
+
+def _conv3x3_done(st: int, out: torch.Tensor, what: str):
+    """Those entries' tail: None for a shape the kernel does not serve (the caller falls
+    back), any other failure raises."""
+    if st == VD_ERR_SHAPE:
+        return None
+    check(st, what)
+    return out
+
+
 def conv3x3_bias_act(x: torch.Tensor, w2: torch.Tensor, bias: Optional[torch.Tensor],
                      relu: bool = False, out: Optional[torch.Tensor] = None):
     """act(conv3x3(x, pad 1) + bias) on a channels_last fp32 tensor in one MFMA
     implicit-GEMM kernel (vd_conv3x3_bias_act); w2 from conv3x3_weight.  Returns
     None for a shape the kernel does not serve (the caller falls back)."""
-    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or \
-            not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("conv3x3_bias_act: x must be a channels_last fp32 CUDA tensor")
-    N, C, H, W = x.shape
+    N, C, H, W = _conv3x3_x(x)
     w_ = _need(w2, "w2")
     Cout = w_.shape[0]
     if tuple(w_.shape) != (Cout, 3, 3, C):
         raise ValueError("w2 must be [Cout][3][3][Cin], got %s" % (tuple(w_.shape),))
-    b_ = _need(bias, "bias") if bias is not None else None
-    if b_ is not None and b_.numel() != Cout:
-        raise ValueError("bias must have %d elements" % Cout)
-    if out is None:
-        out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device,
-                          memory_format=torch.channels_last)
-    elif tuple(out.shape) != (N, Cout, H, W) or \
-            not out.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("out must be a channels_last %s tensor" % ((N, Cout, H, W),))
-    st = lib().vd_conv3x3_bias_act(x.data_ptr(), N, H, W, C, w_.data_ptr(), Cout,
-                                   b_.data_ptr() if b_ is not None else None, int(relu),
-                                   out.data_ptr(), _stream())
-    if st == VD_ERR_SHAPE:
-        return None
-    check(st, "vd_conv3x3_bias_act")
-    return out
+    b, out = _conv3x3_bias_out(x, bias, Cout, out)
+    return _conv3x3_done(lib().vd_conv3x3_bias_act(
+        x.data_ptr(), N, H, W, C, w_.data_ptr(), Cout, _ptr(b), int(relu), out.data_ptr(),
+        _stream()), out, "vd_conv3x3_bias_act")
 
 
 WINO_MAX_CIN = 4096  # csrc/conv3x3_wino.hip: the zero lanes' DMA source holds 4096 floats
+
+
+def wino_serves(Cin: int, Cout: int) -> bool:
+    """The channel counts both Winograd kernels serve: Cout in 64-channel blocks, Cin in
+    8-channel MFMA steps up to WINO_MAX_CIN.  One rule for the weight transforms below
+    and for modeling's route functions."""
+    return Cout > 0 and Cin > 0 and Cout % 64 == 0 and Cin % 8 == 0 and Cin <= WINO_MAX_CIN
 
 
 def conv3x3_wino_weight(w: torch.Tensor) -> Optional[torch.Tensor]:
@@ -782,7 +818,7 @@ def conv3x3_wino_weight(w: torch.Tensor) -> Optional[torch.Tensor]:
     if w_.dim() != 4 or tuple(w_.shape[2:]) != (3, 3):
         raise ValueError("conv3x3_wino_weight: weight %s" % (tuple(w_.shape),))
     Cout, C = w_.shape[:2]
-    if Cout % 64 or C % 8 or Cout == 0 or C == 0 or C > WINO_MAX_CIN:
+    if not wino_serves(C, Cout):
         return None
     u = torch.empty((Cout // 64, C // 8, 2, 16, 64, 4), dtype=torch.float32, device=w_.device)
     check(lib().vd_conv3x3_wino_weight(w_.data_ptr(), Cout, C, u.data_ptr(), _stream()),
@@ -801,36 +837,24 @@ def conv3x3_wino_bias_act(x: torch.Tensor, u: torch.Tensor, bias: Optional[torch
     (vd_conv3x3_wino_mosaic_bias_act; an odd side padded by a phantom row / column
     per map): no idle block columns either.
     Returns None for a shape the kernel does not serve."""
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 \
-            or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("x must be a channels_last fp32 device tensor")
+    N, C, H, W = _conv3x3_x(x)
     if u is None:
         return None
     u_ = _need(u, "u")
-    N, C, H, W = x.shape
     if u_.dim() != 6 or tuple(u_.shape[1:]) != (C // 8, 2, 16, 64, 4) or C % 8:
         raise ValueError("u must be [Cout/64][%d][2][16][64][4], got %s" % (C // 8, tuple(u_.shape)))
     Cout = u_.shape[0] * 64
-    b_ = _need(bias, "bias") if bias is not None else None
-    if out is None:
-        out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device,
-                          memory_format=torch.channels_last)
+    b, out = _conv3x3_bias_out(x, bias, Cout, out)
     if mosaic == "2d" and N > 0:
         st = lib().vd_conv3x3_wino_mosaic_bias_act(x.data_ptr(), N, H, W, C, u_.data_ptr(), Cout,
-                                                   b_.data_ptr() if b_ is not None else None,
-                                                   int(relu), out.data_ptr(), _stream())
+                                                   _ptr(b), int(relu), out.data_ptr(), _stream())
     elif mosaic and N > 0:
         st = lib().vd_conv3x3_wino_seg_bias_act(x.data_ptr(), N * H, W, C, u_.data_ptr(), Cout,
-                                                b_.data_ptr() if b_ is not None else None,
-                                                int(relu), H, out.data_ptr(), _stream())
+                                                _ptr(b), int(relu), H, out.data_ptr(), _stream())
     else:
         st = lib().vd_conv3x3_wino_bias_act(x.data_ptr(), N, H, W, C, u_.data_ptr(), Cout,
-                                            b_.data_ptr() if b_ is not None else None,
-                                            int(relu), out.data_ptr(), _stream())
-    if st == VD_ERR_SHAPE:
-        return None
-    check(st, "vd_conv3x3_wino_bias_act")
-    return out
+                                            _ptr(b), int(relu), out.data_ptr(), _stream())
+    return _conv3x3_done(st, out, "vd_conv3x3_wino_bias_act")
 
 
 def conv3x3_wino4_weight(w: torch.Tensor) -> Optional[torch.Tensor]:
@@ -842,7 +866,7 @@ def conv3x3_wino4_weight(w: torch.Tensor) -> Optional[torch.Tensor]:
     if w_.dim() != 4 or tuple(w_.shape[2:]) != (3, 3):
         raise ValueError("conv3x3_wino4_weight: weight %s" % (tuple(w_.shape),))
     Cout, C = w_.shape[:2]
-    if Cout % 64 or C % 8 or Cout == 0 or C == 0 or C > WINO_MAX_CIN:
+    if not wino_serves(C, Cout):
         return None
     u = torch.empty((Cout // 64, C // 8, 4, 18, 64, 4), dtype=torch.float32, device=w_.device)
     check(lib().vd_conv3x3_wino4_weight(w_.data_ptr(), Cout, C, u.data_ptr(), _stream()),
@@ -880,48 +904,32 @@ def conv3x3_wino4_bias_act(x: torch.Tensor, u: torch.Tensor, bias: Optional[torc
     equal within Winograd rounding).  groups > 1: a grouped conv (u from
     conv3x3_wino4_grouped_weight; mosaic False or "rows").  None for a shape the kernel
     does not serve."""
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 \
-            or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("x must be a channels_last fp32 device tensor")
+    N, C, H, W = _conv3x3_x(x)
     if u is None:
         return None
     u_ = _need(u, "u")
-    N, C, H, W = x.shape
     if groups > 1:
         if u_.dim() != 6 or tuple(u_.shape) != (C // 64, 8, 4, 18, 64, 4) or C % 64:
             raise ValueError("grouped u must be [%d][8][4][18][64][4], got %s"
                              % (C // 64, tuple(u_.shape)))
         if mosaic not in (False, None, "rows"):
             return None
-        b_ = _need(bias, "bias") if bias is not None else None
-        if out is None:
-            out = torch.empty((N, C, H, W), dtype=torch.float32, device=x.device,
-                              memory_format=torch.channels_last)
-        st = lib().vd_conv3x3_wino4_grouped_bias_act(
-            x.data_ptr(), N, H, W, C, u_.data_ptr(), int(groups),
-            b_.data_ptr() if b_ is not None else None, int(relu), out.data_ptr(),
-            int(mosaic == "rows"), _stream())
-        if st == VD_ERR_SHAPE:
-            return None
-        check(st, "vd_conv3x3_wino4_grouped_bias_act")
-        return out
+        b, out = _conv3x3_bias_out(x, bias, C, out)
+        return _conv3x3_done(lib().vd_conv3x3_wino4_grouped_bias_act(
+            x.data_ptr(), N, H, W, C, u_.data_ptr(), int(groups), _ptr(b), int(relu),
+            out.data_ptr(), int(mosaic == "rows"), _stream()), out,
+            "vd_conv3x3_wino4_grouped_bias_act")
     if u_.dim() != 6 or tuple(u_.shape[1:]) != (C // 8, 4, 18, 64, 4) or C % 8:
         raise ValueError("u must be [Cout/64][%d][4][18][64][4], got %s" % (C // 8, tuple(u_.shape)))
     Cout = u_.shape[0] * 64
-    b_ = _need(bias, "bias") if bias is not None else None
-    if out is None:
-        out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device,
-                          memory_format=torch.channels_last)
+    b, out = _conv3x3_bias_out(x, bias, Cout, out)
     fn = {False: lib().vd_conv3x3_wino4_bias_act, True: lib().vd_conv3x3_wino4_mosaic_bias_act,
           "pair": lib().vd_conv3x3_wino4_mosaic_bias_act,
           "rows": lib().vd_conv3x3_wino4_rows_bias_act,
           "grid": lib().vd_conv3x3_wino4_grid_bias_act}[mosaic]
-    st = fn(x.data_ptr(), N, H, W, C, u_.data_ptr(), Cout,
-            b_.data_ptr() if b_ is not None else None, int(relu), out.data_ptr(), _stream())
-    if st == VD_ERR_SHAPE:
-        return None
-    check(st, "vd_conv3x3_wino4_bias_act (mosaic %r)" % (mosaic,))
-    return out
+    return _conv3x3_done(fn(x.data_ptr(), N, H, W, C, u_.data_ptr(), Cout, _ptr(b), int(relu),
+                            out.data_ptr(), _stream()), out,
+                         "vd_conv3x3_wino4_bias_act (mosaic %r)" % (mosaic,))
 
 
 def conv3x3_wino4_plan(N: int, H: int, W: int, C: int, Cout: int, stacked: bool, n_cu: int):
@@ -943,28 +951,18 @@ def conv3x3_wino4_dilated2_bias_act(x: torch.Tensor, u: torch.Tensor,
     place (vd_conv3x3_wino4_dilated2_bias_act); u from conv3x3_wino4_weight.  None for a
     shape the kernel does not serve.  layout: the sub-maps' block layout, False (one
     per block), "pair" (pairs / octets) or "grid"."""
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 \
-            or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("x must be a channels_last fp32 device tensor")
+    N, C, H, W = _conv3x3_x(x)
     lay = {False: 0, None: 0, "pair": 1, True: 1, "grid": 2}.get(layout)
     if lay is None:
         return None
     u_ = _need(u, "u")
-    N, C, H, W = x.shape
     if u_.dim() != 6 or tuple(u_.shape[1:]) != (C // 8, 4, 18, 64, 4) or C % 8 or H % 2 or W % 2:
         return None
     Cout = u_.shape[0] * 64
-    b_ = _need(bias, "bias") if bias is not None else None
-    if out is None:
-        out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device,
-                          memory_format=torch.channels_last)
-    st = lib().vd_conv3x3_wino4_dilated2_bias_act(
-        x.data_ptr(), N, H, W, C, u_.data_ptr(), Cout, b_.data_ptr() if b_ is not None else None,
-        int(relu), out.data_ptr(), lay, _stream())
-    if st == VD_ERR_SHAPE:
-        return None
-    check(st, "vd_conv3x3_wino4_dilated2_bias_act")
-    return out
+    b, out = _conv3x3_bias_out(x, bias, Cout, out)
+    return _conv3x3_done(lib().vd_conv3x3_wino4_dilated2_bias_act(
+        x.data_ptr(), N, H, W, C, u_.data_ptr(), Cout, _ptr(b), int(relu), out.data_ptr(), lay,
+        _stream()), out, "vd_conv3x3_wino4_dilated2_bias_act")
 
 
 def gemm_dual_bias_act(a1: torch.Tensor, a2: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
@@ -1855,24 +1853,14 @@ def flow_to_levels(raw_flow: torch.Tensor, im_scale: float, Hp: int, Wp: int,
     return levels, blob
 
 
-_delta_w_cache: dict = {}
+def _delta_flow_weight(w: torch.Tensor) -> torch.Tensor:
+    return w.detach().permute(2, 3, 0, 1).reshape(18, w.shape[1]).contiguous()
 
 
 def delta_flow_weight_cached(w: torch.Tensor) -> torch.Tensor:
     """A Conv_Delta_Flows_Features weight [2, C, 3, 3] in vd_delta_flow_features'
-    layout [18, C] (row (ky * 3 + kx) * 2 + o), made once per weight tensor and
-    remade when the tensor changes (as split3_weight_cached)."""
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    i = id(w)
-    ent = _delta_w_cache.get(i)
-    if ent is not None and ent[0]() is w and ent[1] == key:
-        return ent[2]
-    def _drop(r, i=i):
-        if _delta_w_cache.get(i, (None,))[0] is r:
-            del _delta_w_cache[i]
-    wp = w.detach().permute(2, 3, 0, 1).reshape(18, w.shape[1]).contiguous()
-    _delta_w_cache[i] = (weakref.ref(w, _drop), key, wp)
-    return wp
+    layout [18, C] (row (ky * 3 + kx) * 2 + o), through _weight_cached."""
+    return _weight_cached(w, _delta_flow_weight)
 
 
 def delta_flow_features(feats: Sequence[torch.Tensor], weights: Sequence[torch.Tensor],
