@@ -208,6 +208,34 @@ int vd_mask_head_upconv_logits(const float *X, int M, int K, const void *Wp, con
                                const float *cls_w, const float *cls_b, const int32_t *roi_ch,
                                int P, float *masks, void *stream);
 
+/* vd_gemm_split3_bias_act's GEMM with three fp16 products per fp32 product instead of
+ * six bf16 ones (csrc/gemm_split3.hip, SCH = 1; the error-corrected fp16 scheme of Ootomo
+ * & Yokota with one common scale): with S = 2^11, A is split into a0 = fp16(a) and a1 =
+ * fp16(S (a - a0)) as it is loaded, the weight row n is scaled by the power of two r_n
+ * that brings its largest magnitude into [1, 2) and kept as Wm = fp16(S r_n w), Wr =
+ * fp16(S r_n w - Wm), W0 = fp16(r_n w); acc += a0 Wr + a1 W0 + a0 Wm on
+ * v_mfma_f32_32x32x16_f16, then acc / (S r_n) (exact), bias, residual, ReLU as above.
+ * Wp: vd_gemm_h2_weight_size(N, K) bytes (the three images, N * K * 6, then N floats
+ * 1 / (S r_n)), made once per weight by vd_gemm_h2_weight.  Same arguments, shapes,
+ * cfg 0-5 and status codes as vd_gemm_split3_bias_act.
+ * Input contract: the result is at fp32's error level (tests/test_gemm_h2_gpu.py: against
+ * fp64 beside torch's fp32 GEMM) for activations whose largest magnitude lies in
+ * [2^-10, 65504].  An activation above 65504 makes a0 infinite and its output row
+ * non-finite, never a finite wrong value; below 2^-10 the per-element floor of 2^-36
+ * (fp16's subnormal spacing under the scale S) shows against the result.  Weights of any
+ * finite fp32 magnitude are covered by the row scale (a row of fp32 subnormals only is
+ * scaled as if its largest magnitude were 2^-126).  vd_mask_head_upconv_logits_h2 is
+ * vd_mask_head_upconv_logits on this scheme (Wp from vd_gemm_h2_weight). */
+size_t vd_gemm_h2_weight_size(int N, int K);
+int vd_gemm_h2_weight(const float *W, int N, int K, void *Wp, void *stream);
+int vd_gemm_h2_bias_act(const float *A, int M, int K, const float *A2, int K2,
+                        const float *a_bias, const void *Wp, int N, const float *bias,
+                        const float *residual, int up_h, int up_w, int sub_h, int sub_w,
+                        int relu, float *D, int cfg, void *stream);
+int vd_mask_head_upconv_logits_h2(const float *X, int M, int K, const void *Wp,
+                                  const float *bias, const float *cls_w, const float *cls_b,
+                                  const int32_t *roi_ch, int P, float *masks, void *stream);
+
 /* 3x3 stride-1 pad-1 convolution of a channels_last (NHWC) fp32 tensor with
  * the bias (+ ReLU) epilogue fused, one hand-written MFMA implicit-GEMM kernel:
  * Y[n][y][x][co] = act(sum_{ky,kx,ci} X[n][y+ky-1][x+kx-1][ci] W2[co][ky][kx][ci]

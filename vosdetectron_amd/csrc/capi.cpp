@@ -158,6 +158,33 @@ int vd_mask_head_upconv_logits(const float *X, int M, int K, const void *Wp, con
                                           VD_STREAM(stream));
 }
 
+size_t vd_gemm_h2_weight_size(int N, int K) {
+    return (N > 0 && K > 0 && gemm_split3_supported(K, N)) ? gemm_h2_weight_bytes(N, K) : 0;
+}
+
+int vd_gemm_h2_weight(const float *W, int N, int K, void *Wp, void *stream) {
+    if (N < 1 || K < 1 || !W || !Wp) return VD_ERR_ARG;
+    return launch_gemm_h2_weight(W, N, K, Wp, VD_STREAM(stream));
+}
+
+int vd_gemm_h2_bias_act(const float *A, int M, int K, const float *A2, int K2,
+                        const float *a_bias, const void *Wp, int N, const float *bias,
+                        const float *residual, int up_h, int up_w, int sub_h, int sub_w,
+                        int relu, float *D, int cfg, void *stream) {
+    if (M < 0 || K < 1 || N < 1 || !Wp || !bias || !D || (M > 0 && !A) || cfg < 0 || cfg > 5)
+        return VD_ERR_ARG;
+    return launch_gemm_h2(A, M, K, A2, K2, Wp, N, bias, residual, up_h, up_w, sub_h, sub_w, relu,
+                          D, cfg, VD_STREAM(stream), a_bias);
+}
+
+int vd_mask_head_upconv_logits_h2(const float *X, int M, int K, const void *Wp,
+                                  const float *bias, const float *cls_w, const float *cls_b,
+                                  const int32_t *roi_ch, int P, float *masks, void *stream) {
+    if (M < 0 || K < 1 || P < 1 || !Wp || !bias || !masks || (M > 0 && !X)) return VD_ERR_ARG;
+    return launch_gemm_h2_mask_logits(X, M, K, Wp, 1024, bias, cls_w, cls_b, roi_ch, P, masks,
+                                      VD_STREAM(stream));
+}
+
 int vd_conv3x3_bias_act(const float *X, int N, int H, int W, int C, const float *W2, int Cout,
                         const float *bias, int relu, float *Y, void *stream) {
     if (N < 0 || H < 1 || W < 1 || C < 1 || Cout < 1 || !W2 || !Y || (N > 0 && !X))

@@ -55,6 +55,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f2v __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kStep = 16;           // fp32 K per pipeline stage (one MFMA k-step)
 constexpr int kFragBytes = 1024;    // one lane-linear 32 x 16 bf16 fragment
@@ -75,6 +77,84 @@ __device__ __forceinline__ void split_pair(float x0, float x1, uint32_t &p0, uin
     p0 = uh;
     p1 = um;
     p2 = __builtin_bit_cast(uint32_t, l);
+}
+
+// The two-piece fp16 scheme (SCH = 1; the error-corrected fp16 product of Ootomo &
+// Yokota, "Recovering single precision accuracy from Tensor Cores while surpassing the
+// FP32 theoretical peak performance", IJHPCA 2022, with one common scale so a single
+// accumulator serves): S = 2^11, fp16 carries 11 significant bits, so
+//   a  = a0 + a1 / S,   a0 = fp16(a),  a1 = fp16(S (a - a0))        (|err| <= 2^-22 |a|)
+//   S r w = Wm + Wr,    Wm = fp16(S r w), Wr = fp16(S r w - Wm),  W0 = fp16(r w)
+// with r = 2^-e the power of two that brings the weight row's largest magnitude into
+// [1, 2), and
+//   S r (a . w) ~= a0 Wr + a1 W0 + a0 Wm
+// three v_mfma_f32_32x32x16_f16 into one accumulator (the dropped a1 Wr / S is <= 2^-22
+// of the product), scaled by the exact power of two 1 / (S r) in the epilogue.
+// Activations: largest magnitude in [2^-10, 65504] (include/vosdet.h states the contract).
+constexpr float kH2S = 2048.f;
+
+// Two fp32 -> two packed fp16 pairs (a0, a1), round to nearest even.
+__device__ __forceinline__ void split_pair_h2(float x0, float x1, uint32_t &p0, uint32_t &p1) {
+    const f2v x = {x0, x1};
+    const f16x2 h = __builtin_convertvector(x, f16x2);
+    const f2v r = (x - __builtin_convertvector(h, f2v)) * kH2S;  // exact
+    p0 = __builtin_bit_cast(uint32_t, h);
+    p1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+}
+
+// ReLU of an epilogue: SCH 1 keeps a NaN (an activation beyond fp16's range makes a0 Wm and
+// a1 W0 opposite infinities), so such a row leaves the kernel non-finite, never as 0
+template <int SCH>
+__device__ __forceinline__ float relu_sch(float x) {
+    if constexpr (SCH) return x < 0.f ? 0.f : x;
+    return fmaxf(x, 0.f);
+}
+
+// scale[n] = 1 / (S r_n) = 2^(e - 11), e the exponent of row n's largest magnitude (0 for
+// an all-zero row; held to fp32's normal range [-126, 127]: a row of fp32 subnormals only
+// is scaled as if its largest magnitude were 2^-126).  One wave per row.
+__global__ void h2_row_scale_kernel(const float *__restrict__ W, int N, int K,
+                                    float *__restrict__ scale) {
+    const int n = blockIdx.x;
+    float m = 0.f;
+    for (int k = threadIdx.x; k < K; k += 64) m = fmaxf(m, fabsf(W[(int64_t)n * K + k]));
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (threadIdx.x == 0) {
+        int e = m > 0.f ? ilogbf(m) : 0;
+        e = e < -126 ? -126 : (e > 127 ? 127 : e);
+        scale[n] = ldexpf(1.f, e - 11);
+    }
+}
+
+// W [N][K] fp32 -> Wp: [K / 16][N / 32][image 3 (Wm, Wr, W0)][lane 64][8] fp16, the lane
+// order of split3_weight_kernel.
+__global__ void h2_weight_kernel(const float *__restrict__ W, int N, int K,
+                                 const float *__restrict__ scale, uint4 *__restrict__ Wp) {
+    const int64_t cells = (int64_t)(K / kStep) * (N / 32) * 64;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cells;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(i & 63);
+        const int64_t st = i >> 6;
+        const int t = (int)(st % (N / 32)), s = (int)(st / (N / 32));
+        const int n = 32 * t + (lane & 31), k = kStep * s + 8 * (lane >> 5);
+        const float *w = W + (int64_t)n * K + k;
+        const int e = ilogbf(scale[n]) + 11;
+        uint32_t q[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f2v x = {ldexpf(w[2 * j], 11 - e), ldexpf(w[2 * j + 1], 11 - e)};
+            const f2v y = {ldexpf(w[2 * j], -e), ldexpf(w[2 * j + 1], -e)};
+            const f16x2 m = __builtin_convertvector(x, f16x2);
+            const f2v r = x - __builtin_convertvector(m, f2v);  // exact
+            q[0][j] = __builtin_bit_cast(uint32_t, m);
+            q[1][j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+            q[2][j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(y, f16x2));
+        }
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+            Wp[(st * 3 + p) * 64 + lane] = make_uint4(q[p][0], q[p][1], q[p][2], q[p][3]);
+    }
 }
 
 // W [N][K] fp32 -> Wp: [K / 16][N / 32][piece 3][lane 64][8] bf16, lane l = 32 h + r
@@ -113,8 +193,10 @@ __global__ void split3_weight_kernel(const float *__restrict__ W, int N, int K,
 // classify weights [classes][256], cb its bias, rch each RoI's class channel, H = P
 // (the RoI map side), D = masks [RoIs][2P][2P]; the relu'd upconv output never leaves
 // the workgroup.
+// SCH: 0 = three bf16 pieces per operand, six products; 1 = the two-piece fp16 scheme
+// above (A in two pieces, Wp the h2 image with its N scales behind it, three products).
 template <int BM, int BN, int TPM, int TPN, int RES, bool RELU, int PROBE = 0, int OCC = 1,
-          int NW = 4, bool APRO = false>
+          int NW = 4, bool APRO = false, int SCH = 0>
 __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
     const float *__restrict__ A, const uint4 *__restrict__ Wp, const float *__restrict__ bias,
     const float *__restrict__ R, float *__restrict__ D, int M, int N, int K, int tiles_n,
@@ -124,7 +206,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
     constexpr int WM = BM / (32 * TPM), WN = BN / (32 * TPN), NTH = 64 * NW;
     static_assert(WM * WN == NW, "one (pixel, channel) block per wave");
     constexpr int PT = BM / 32, NTW = BN / 32;                 // pixel / channel tiles
-    constexpr int A_BYTES = 3 * PT * kFragBytes;               // [piece][pt][lane]
+    constexpr int NPA = SCH ? 2 : 3;                           // A pieces
+    constexpr int A_BYTES = NPA * PT * kFragBytes;             // [piece][pt][lane]
     constexpr int W_BYTES = NTW * 3 * kFragBytes;              // [tw][piece][lane]
     constexpr int BUF = A_BYTES + W_BYTES;
     constexpr int AL = BM * kStep / 4 / NTH;                   // A float4 loads per thread
@@ -210,13 +293,19 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
         _Pragma("unroll") for (int j = 0; j < AL; ++j) {                                  \
             const int row = (t >> 2) + RPJ * j, pt = row >> 5, r = row & 31;              \
             uint32_t p00, p10, p20, p01, p11, p21;                                        \
-            split_pair(ar[j].x, ar[j].y, p00, p10, p20);                                  \
-            split_pair(ar[j].z, ar[j].w, p01, p11, p21);                                  \
+            if constexpr (SCH) {                                                          \
+                split_pair_h2(ar[j].x, ar[j].y, p00, p10);                                \
+                split_pair_h2(ar[j].z, ar[j].w, p01, p11);                                \
+            } else {                                                                      \
+                split_pair(ar[j].x, ar[j].y, p00, p10, p20);                              \
+                split_pair(ar[j].z, ar[j].w, p01, p11, p21);                              \
+            }                                                                             \
             const int off = (pt * 64 + (kq >> 1) * 32 + r) * 16 + (kq & 1) * 8;           \
             *reinterpret_cast<uint2 *>(base_ + off) = make_uint2(p00, p01);               \
             *reinterpret_cast<uint2 *>(base_ + PT * kFragBytes + off) = make_uint2(p10, p11); \
-            *reinterpret_cast<uint2 *>(base_ + 2 * PT * kFragBytes + off) =               \
-                make_uint2(p20, p21);                                                     \
+            if constexpr (!SCH)                                                           \
+                *reinterpret_cast<uint2 *>(base_ + 2 * PT * kFragBytes + off) =           \
+                    make_uint2(p20, p21);                                                 \
         }                                                                                 \
         _Pragma("unroll") for (int j = 0; j < WL; ++j) {                                  \
             const int i = t + NTH * j;                                                    \
@@ -247,7 +336,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
 #pragma unroll
         for (int a = 0; a < TPM; ++a)
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
+            for (int q = 0; q < NPA; ++q)
                 af[a][q] = *reinterpret_cast<const bf16x8 *>(
                     base + (q * PT + wm * TPM + a) * kFragBytes + lane * 16);
 #pragma unroll
@@ -266,6 +355,18 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
                     continue;
                 }
                 f32x16 x = acc[a][b];
+                if constexpr (SCH) {  // a0 Wr + a1 W0 + a0 Wm, smallest terms first
+                    const f16x8 a0 = __builtin_bit_cast(f16x8, af[a][0]);
+                    x = __builtin_amdgcn_mfma_f32_32x32x16_f16(
+                        __builtin_bit_cast(f16x8, wf[b][1]), a0, x, 0, 0, 0);
+                    x = __builtin_amdgcn_mfma_f32_32x32x16_f16(
+                        __builtin_bit_cast(f16x8, wf[b][2]),
+                        __builtin_bit_cast(f16x8, af[a][1]), x, 0, 0, 0);
+                    x = __builtin_amdgcn_mfma_f32_32x32x16_f16(
+                        __builtin_bit_cast(f16x8, wf[b][0]), a0, x, 0, 0, 0);
+                    acc[a][b] = x;
+                    continue;
+                }
                 x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[b][2], af[a][0], x, 0, 0, 0);
                 x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[b][1], af[a][1], x, 0, 0, 0);
                 x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[b][0], af[a][2], x, 0, 0, 0);
@@ -286,6 +387,23 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
 
     // epilogue: lane = pixel (r), registers 4g..4g+3 = channels 8g + 4h .. + 3
     const int h = lane >> 5, r = lane & 31;
+    if constexpr (SCH) {  // acc * 1 / (S r_n): an exact power of two per output channel
+        const float *scale = reinterpret_cast<const float *>(Wp + (int64_t)N * (K / kStep) * 6);
+#pragma unroll
+        for (int b = 0; b < TPN; ++b)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 sc = *reinterpret_cast<const float4 *>(
+                    scale + n0 + (wn * TPN + b) * 32 + 4 * h + 8 * g);
+#pragma unroll
+                for (int a = 0; a < TPM; ++a) {
+                    acc[a][b][4 * g] *= sc.x;
+                    acc[a][b][4 * g + 1] *= sc.y;
+                    acc[a][b][4 * g + 2] *= sc.z;
+                    acc[a][b][4 * g + 3] *= sc.w;
+                }
+            }
+    }
     if constexpr (RES == 3) {
         static_assert(BN == 256 && RELU, "one (i, j) group per workgroup");
         // per pixel: sum over this wave's 128 channels of relu(acc + b) * Wc[class][co],
@@ -306,10 +424,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
                 for (int g = 0; g < 4; ++g) {
                     const float4 bb = *reinterpret_cast<const float4 *>(bias + n0 + cl + 8 * g);
                     const float4 ww = *reinterpret_cast<const float4 *>(wc + cl + 8 * g);
-                    sacc += fmaxf(acc[a][b][4 * g] + bb.x, 0.f) * ww.x;
-                    sacc += fmaxf(acc[a][b][4 * g + 1] + bb.y, 0.f) * ww.y;
-                    sacc += fmaxf(acc[a][b][4 * g + 2] + bb.z, 0.f) * ww.z;
-                    sacc += fmaxf(acc[a][b][4 * g + 3] + bb.w, 0.f) * ww.w;
+                    sacc += relu_sch<SCH>(acc[a][b][4 * g] + bb.x) * ww.x;
+                    sacc += relu_sch<SCH>(acc[a][b][4 * g + 1] + bb.y) * ww.y;
+                    sacc += relu_sch<SCH>(acc[a][b][4 * g + 2] + bb.z) * ww.z;
+                    sacc += relu_sch<SCH>(acc[a][b][4 * g + 3] + bb.w) * ww.w;
                 }
             }
             dot[a] = sacc + __shfl_xor(sacc, 32);
@@ -364,10 +482,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
                     o.w += rr.w;
                 }
                 if (RELU) {
-                    o.x = fmaxf(o.x, 0.f);
-                    o.y = fmaxf(o.y, 0.f);
-                    o.z = fmaxf(o.z, 0.f);
-                    o.w = fmaxf(o.w, 0.f);
+                    o.x = relu_sch<SCH>(o.x);
+                    o.y = relu_sch<SCH>(o.y);
+                    o.z = relu_sch<SCH>(o.z);
+                    o.w = relu_sch<SCH>(o.w);
                 }
                 *reinterpret_cast<float4 *>(D + p * N + ch) = o;
             }
@@ -376,15 +494,15 @@ __global__ __launch_bounds__(64 * NW, OCC) void gemm_split3_kernel(
 }
 
 template <int BM, int BN, int TPM, int TPN, int RES, bool RELU, int PROBE = 0, int OCC = 1,
-          int NW = 4, bool APRO = false>
+          int NW = 4, bool APRO = false, int SCH = 0>
 int launch_cfg(const float *A, int M, int K, const uint4 *Wp, int N, const float *bias,
                const float *R, float *D, int H, int W, int SH, int SW, hipStream_t s,
                const float *cb = nullptr, const int32_t *rch = nullptr,
                const float *A2 = nullptr, int K2 = 0, const float *abias = nullptr) {
     constexpr int PT = BM / 32, NTW = BN / 32;
-    constexpr size_t lds = 2 * (size_t)(3 * PT + NTW * 3) * kFragBytes;
+    constexpr size_t lds = 2 * (size_t)((SCH ? 2 : 3) * PT + NTW * 3) * kFragBytes;
     static_assert(lds <= VD_LDS_BYTES, "LDS");
-    auto kern = gemm_split3_kernel<BM, BN, TPM, TPN, RES, RELU, PROBE, OCC, NW, APRO>;
+    auto kern = gemm_split3_kernel<BM, BN, TPM, TPN, RES, RELU, PROBE, OCC, NW, APRO, SCH>;
     static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lds) == hipSuccess;
@@ -398,24 +516,24 @@ int launch_cfg(const float *A, int M, int K, const uint4 *Wp, int N, const float
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 
-template <int BM, int BN, int TPM, int TPN, int OCC, int NW = 4>
+template <int SCH, int BM, int BN, int TPM, int TPN, int OCC, int NW = 4>
 int launch_epi(const float *A, int M, int K, const uint4 *Wp, int N, const float *bias,
                const float *R, int relu, float *D, int H, int W, int SH, int SW, hipStream_t s,
                const float *A2, int K2, const float *abias) {
 #define VD_S3_RELU(RES_)                                                                       \
-    return relu ? launch_cfg<BM, BN, TPM, TPN, RES_, true, 0, OCC, NW>(                        \
+    return relu ? launch_cfg<BM, BN, TPM, TPN, RES_, true, 0, OCC, NW, false, SCH>(            \
                       A, M, K, Wp, N, bias, R, D, H, W, SH, SW, s, nullptr, nullptr, A2, K2,   \
                       abias)                                                                   \
-                : launch_cfg<BM, BN, TPM, TPN, RES_, false, 0, OCC, NW>(                       \
+                : launch_cfg<BM, BN, TPM, TPN, RES_, false, 0, OCC, NW, false, SCH>(           \
                       A, M, K, Wp, N, bias, R, D, H, W, SH, SW, s, nullptr, nullptr, A2, K2,   \
                       abias)
     if (abias) {  // the A prologue: compiled only where it is used (conv3 after a
                   // grouped conv2: ReLU, with or without a residual)
         if (!relu || (R && H > 0)) return VD_ERR_ARG;
         if (R)
-            return launch_cfg<BM, BN, TPM, TPN, 1, true, 0, OCC, NW, true>(
+            return launch_cfg<BM, BN, TPM, TPN, 1, true, 0, OCC, NW, true, SCH>(
                 A, M, K, Wp, N, bias, R, D, H, W, SH, SW, s, nullptr, nullptr, A2, K2, abias);
-        return launch_cfg<BM, BN, TPM, TPN, 0, true, 0, OCC, NW, true>(
+        return launch_cfg<BM, BN, TPM, TPN, 0, true, 0, OCC, NW, true, SCH>(
             A, M, K, Wp, N, bias, R, D, H, W, SH, SW, s, nullptr, nullptr, A2, K2, abias);
     }
     if (R && H > 0) VD_S3_RELU(2);
@@ -423,6 +541,11 @@ int launch_epi(const float *A, int M, int K, const uint4 *Wp, int N, const float
     VD_S3_RELU(0);
 #undef VD_S3_RELU
 }
+
+template <int SCH>
+int launch_gemm_sch(const float *A, int M, int K, const float *A2, int K2, const void *Wp, int N,
+                    const float *bias, const float *R, int up_h, int up_w, int sub_h, int sub_w,
+                    int relu, float *D, int cfg, hipStream_t s, const float *a_bias);
 
 }  // namespace
 
@@ -452,6 +575,40 @@ int launch_gemm_split3(const float *A, int M, int K, const float *A2, int K2, co
                        int N, const float *bias, const float *R, int up_h, int up_w, int sub_h,
                        int sub_w, int relu, float *D, int cfg, hipStream_t s,
                        const float *a_bias) {
+    return launch_gemm_sch<0>(A, M, K, A2, K2, Wp, N, bias, R, up_h, up_w, sub_h, sub_w, relu, D,
+                              cfg, s, a_bias);
+}
+
+// The same GEMM on the two-piece fp16 scheme: Wp from launch_gemm_h2_weight.  cfg as above
+// (1-5; no probes).
+int launch_gemm_h2(const float *A, int M, int K, const float *A2, int K2, const void *Wp, int N,
+                   const float *bias, const float *R, int up_h, int up_w, int sub_h, int sub_w,
+                   int relu, float *D, int cfg, hipStream_t s, const float *a_bias) {
+    if (cfg < 0 || cfg > 5) return VD_ERR_ARG;
+    return launch_gemm_sch<1>(A, M, K, A2, K2, Wp, N, bias, R, up_h, up_w, sub_h, sub_w, relu, D,
+                              cfg, s, a_bias);
+}
+
+size_t gemm_h2_weight_bytes(int N, int K) { return (size_t)N * K * 6 + (size_t)N * 4; }
+
+// Wp: the three fp16 images (N * K * 6 bytes), then the N row scales 1 / (S r_n)
+int launch_gemm_h2_weight(const float *W, int N, int K, void *Wp, hipStream_t s) {
+    if (!gemm_split3_supported(K, N)) return VD_ERR_SHAPE;
+    float *scale = reinterpret_cast<float *>(static_cast<unsigned char *>(Wp) + (size_t)N * K * 6);
+    hipLaunchKernelGGL(h2_row_scale_kernel, dim3((unsigned)N), dim3(64), 0, s, W, N, K, scale);
+    const int64_t cells = (int64_t)(K / kStep) * (N / 32) * 64;
+    const int64_t blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(h2_weight_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)),
+                       dim3(256), 0, s, W, N, K, scale, reinterpret_cast<uint4 *>(Wp));
+    return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
+}
+
+namespace {
+
+template <int SCH>
+int launch_gemm_sch(const float *A, int M, int K, const float *A2, int K2, const void *Wp, int N,
+                    const float *bias, const float *R, int up_h, int up_w, int sub_h, int sub_w,
+                    int relu, float *D, int cfg, hipStream_t s, const float *a_bias) {
     if (M == 0) return VD_OK;
     if (!gemm_split3_supported(K, N)) return VD_ERR_SHAPE;
     if (K2 < 0 || K2 >= K || (K2 && (!A2 || K2 % kStep || sub_h || sub_w))) return VD_ERR_ARG;
@@ -494,35 +651,35 @@ int launch_gemm_split3(const float *A, int M, int K, const float *A2, int K2, co
     switch (cfg) {
     case 1:
         if (N % 256) return VD_ERR_SHAPE;
-        return launch_epi<256, 256, 4, 4, 1>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
+        return launch_epi<SCH, 256, 256, 4, 4, 1>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
                                              s, A2, K2, a_bias);
     case 2:
         if (N % 128) return VD_ERR_SHAPE;
-        return launch_epi<256, 128, 4, 2, 2>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
+        return launch_epi<SCH, 256, 128, 4, 2, 2>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
                                              s, A2, K2, a_bias);
     case 5:
         if (N % 256) return VD_ERR_SHAPE;
-        return launch_epi<256, 256, 4, 2, 1, 8>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h,
+        return launch_epi<SCH, 256, 256, 4, 2, 1, 8>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h,
                                                 sub_w, s, A2, K2, a_bias);
     case 4:
         if (N % 128) return VD_ERR_SHAPE;
-        return launch_epi<128, 128, 2, 2, 3>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
+        return launch_epi<SCH, 128, 128, 2, 2, 3>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
                                              s, A2, K2, a_bias);
     case 3:
-        return launch_epi<256, 64, 4, 1, 2>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
+        return launch_epi<SCH, 256, 64, 4, 1, 2>(A, M, K, w, N, bias, R, relu, D, up_h, up_w, sub_h, sub_w,
                                              s, A2, K2, a_bias);
 #ifdef VD_RESEARCH_PROBES
     case 11: case 12: case 13:  // speed-of-light probes of cfg 1 (wrong results by design)
-        if (N % 256 || R || !relu) return VD_ERR_SHAPE;
+        if (SCH || N % 256 || R || !relu) return VD_ERR_SHAPE;
         if (cfg == 11) return launch_cfg<256, 256, 4, 4, 0, true, 1>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
         if (cfg == 12) return launch_cfg<256, 256, 4, 4, 0, true, 2>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
         return launch_cfg<256, 256, 4, 4, 0, true, 3>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
     case 14: case 15:  // cfg 2: MFMA stream alone (fragments read once), without / with barriers
-        if (N % 128 || R || !relu) return VD_ERR_SHAPE;
+        if (SCH || N % 128 || R || !relu) return VD_ERR_SHAPE;
         if (cfg == 14) return launch_cfg<256, 128, 4, 2, 0, true, 4, 2>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
         return launch_cfg<256, 128, 4, 2, 0, true, 5, 2>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
     case 16: case 17: case 18:  // the same probes of cfg 2
-        if (N % 128 || R || !relu) return VD_ERR_SHAPE;
+        if (SCH || N % 128 || R || !relu) return VD_ERR_SHAPE;
         if (cfg == 16) return launch_cfg<256, 128, 4, 2, 0, true, 1, 2>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
         if (cfg == 17) return launch_cfg<256, 128, 4, 2, 0, true, 2, 2>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
         return launch_cfg<256, 128, 4, 2, 0, true, 3, 2>(A, M, K, w, N, bias, R, D, 0, 0, 0, 0, s);
@@ -531,6 +688,8 @@ int launch_gemm_split3(const float *A, int M, int K, const float *A2, int K2, co
         return VD_ERR_ARG;
     }
 }
+
+}  // namespace
 
 int launch_gemm_split3_mask_logits(const float *A, int M, int K, const void *Wp, int N,
                                    const float *bias, const float *cls_w, const float *cls_b,
@@ -542,6 +701,17 @@ int launch_gemm_split3_mask_logits(const float *A, int M, int K, const void *Wp,
                                                         reinterpret_cast<const uint4 *>(Wp), N,
                                                         bias, cls_w, masks, P, P, 0, 0, s, cls_b,
                                                         roi_ch);
+}
+
+int launch_gemm_h2_mask_logits(const float *A, int M, int K, const void *Wp, int N,
+                               const float *bias, const float *cls_w, const float *cls_b,
+                               const int32_t *roi_ch, int P, float *masks, hipStream_t s) {
+    if (M == 0) return VD_OK;
+    if (N != 4 * 256 || !gemm_split3_supported(K, N)) return VD_ERR_SHAPE;
+    if (P < 1 || M % (P * P) || !cls_w || !cls_b || !roi_ch || !masks) return VD_ERR_ARG;
+    return launch_cfg<256, 256, 4, 2, 3, true, 0, 1, 8, false, 1>(
+        A, M, K, reinterpret_cast<const uint4 *>(Wp), N, bias, cls_w, masks, P, P, 0, 0, s, cls_b,
+        roi_ch);
 }
 
 }  // namespace vd

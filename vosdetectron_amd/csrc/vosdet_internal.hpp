@@ -66,6 +66,14 @@ int launch_gemm_split3(const float *A, int M, int K, const float *A2, int K2, co
 int launch_gemm_split3_mask_logits(const float *A, int M, int K, const void *Wp, int N,
                                    const float *bias, const float *cls_w, const float *cls_b,
                                    const int32_t *roi_ch, int P, float *masks, hipStream_t s);
+size_t gemm_h2_weight_bytes(int N, int K);
+int launch_gemm_h2_weight(const float *W, int N, int K, void *Wp, hipStream_t s);
+int launch_gemm_h2(const float *A, int M, int K, const float *A2, int K2, const void *Wp, int N,
+                   const float *bias, const float *R, int up_h, int up_w, int sub_h, int sub_w,
+                   int relu, float *D, int cfg, hipStream_t s, const float *a_bias);
+int launch_gemm_h2_mask_logits(const float *A, int M, int K, const void *Wp, int N,
+                               const float *bias, const float *cls_w, const float *cls_b,
+                               const int32_t *roi_ch, int P, float *masks, hipStream_t s);
 bool gemm1x1_mfma_supported(int K, int N);
 bool conv3x3_mfma_supported(int C, int Cout);
 int launch_conv3x3_mfma(const float *X, int N, int H, int W, int C, const float *W2, int Cout,

@@ -936,9 +936,13 @@ class Roi2MLPHead(nn.Module):
         x = x.reshape(x.size(0), -1)
         if x.is_cuda and x.dtype == torch.float32 and x.size(0) > 0:
             # ReLU in the GEMM epilogue, the plan pinned per shape (ops.gemm_bias_act)
-            y = ops.gemm_bias_act(x.contiguous(), self.fc1_nhwc_weight, self.fc1.bias, relu=True)
+            # (h2: the heads' GEMMs on three fp16 products; the body, FPN and RPN keep the
+            # six-product kernel -- they feed the proposal ranking and NMS, where any change
+            # of rounding moves the step's detections, profiles/gemm_h2/README.md)
+            y = ops.gemm_bias_act(x.contiguous(), self.fc1_nhwc_weight, self.fc1.bias, relu=True,
+                                  h2=True)
             if y is not None:
-                z = ops.gemm_bias_act(y, self.fc2.weight, self.fc2.bias, relu=True)
+                z = ops.gemm_bias_act(y, self.fc2.weight, self.fc2.bias, relu=True, h2=True)
                 if z is not None:
                     return z
         x = F.relu(F.linear(x, self.fc1_nhwc_weight, self.fc1.bias), inplace=True)
@@ -995,7 +999,8 @@ class RoiXconv1fcGNHead(nn.Module):
         y = y.permute(0, 2, 3, 1).reshape(R, -1)
         # fc + ReLU in one GEMM launch (split-bf16 at K = 12,544; torch's hipBLASLt GEMM
         # took 2.7 ms per 16-frame VOS step)
-        z = ops.gemm_bias_act(y.contiguous(), self.fc_nhwc_weight, self.fc.bias, relu=True)
+        z = ops.gemm_bias_act(y.contiguous(), self.fc_nhwc_weight, self.fc.bias, relu=True,
+                              h2=True)
         if z is not None:
             return z
         return F.relu(F.linear(y, self.fc_nhwc_weight, self.fc.bias), inplace=True)
@@ -1035,7 +1040,7 @@ class FastRCNNOutputs(nn.Module):
             # 324 padded to 448: a multiple of the 64-channel tile) on the split-bf16
             # kernel; hipBLASLt ran the two skinny GEMMs at ~0.1 of the fp32 peak
             w, b = self._cat_weights()
-            y = ops.gemm_bias_act(x.contiguous(), w, b, relu=False)
+            y = ops.gemm_bias_act(x.contiguous(), w, b, relu=False, h2=True)
             if y is not None:
                 nc, nb = self.cls_score.out_features, self.bbox_pred.out_features
                 return F.softmax(y[:, :nc], dim=1), y[:, nc:nc + nb].contiguous()
@@ -1120,7 +1125,9 @@ class MaskHeadV1upXconvs(nn.Module):
                 cw.shape[1] == 256 and M > 0:
             x = self._convs_nhwc(x_nhwc.permute(0, 3, 1, 2))
             x = x.permute(0, 2, 3, 1).reshape(M * P * P, -1)
-            wp = ops.split3_weight_cached(self.up_wt)
+            # (the tail's GEMM is M x 1024 x 256 at any RoI count)
+            wp = ops.h2_weight_cached(self.up_wt) if ops.h2_route(M * P * P, 1024, 256) else \
+                ops.split3_weight_cached(self.up_wt)
             if wp is not None:
                 ch = outs._channel(cls_idx).to(torch.int32)
                 return ops.mask_head_upconv_logits(x.contiguous(), wp, self.up_b,

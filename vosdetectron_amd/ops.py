@@ -580,16 +580,56 @@ def split3_weight_cached(w: torch.Tensor) -> Optional[torch.Tensor]:
     return _weight_cached(w, gemm_split3_weight, "VOSDET_SPLIT3_TRACE")
 
 
+def h2_enabled() -> bool:
+    """VOSDET_GEMM_H2=0 keeps the split GEMMs on the six-product bf16 kernel (A/B runs);
+    VOSDET_GEMM_SPLIT3=0 switches both schemes off."""
+    return split3_enabled() and os.environ.get("VOSDET_GEMM_H2", "1") != "0"
+
+
+def h2_route(M: int, N: int, K: int) -> bool:
+    """A split GEMM whose caller asks for the two-piece fp16 scheme (gemm_h2_bias_act)
+    runs there: a function of the shape alone, so a captured graph replays what it
+    captured.  From K = SPLIT3_MIN_K (below it the fp16 pieces' representation error
+    shows, and those GEMMs are HBM-bound).  Every shape class of the 64-frame step is
+    faster there, the HBM-bound K = 256 -> 64 res2 conv1 by 1.1x
+    (profiles/gemm_h2/README.md), so no class is held back."""
+    return h2_enabled() and K >= SPLIT3_MIN_K and K % 16 == 0 and N % 64 == 0 and M > 0
+
+
+def h2_weight_cached(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """gemm_h2_weight(w) through _weight_cached (VOSDET_SPLIT3_TRACE=1 reports each)."""
+    return _weight_cached(w, gemm_h2_weight, "VOSDET_SPLIT3_TRACE")
+
+
+def split_gemm_bias_act(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, h2: bool = False,
+                        **kw) -> Optional[torch.Tensor]:
+    """gemm_split3_bias_act of the weight tensor w [N, K] (its image cached per tensor),
+    or with h2 and h2_route(M, N, K) gemm_h2_bias_act.  M is the output row count (a
+    quarter of a's rows with sub_hw).  None when the shape is not served."""
+    N, K = w.shape[0], w[0].numel()
+    M = a.shape[0]
+    if kw.get("sub_hw") is not None:
+        sh, sw = kw["sub_hw"]
+        M = M // (sh * sw) * ((sh + 1) // 2) * ((sw + 1) // 2)
+    if h2 and h2_route(M, N, K):
+        wp = h2_weight_cached(w)
+        return None if wp is None else gemm_h2_bias_act(a, wp, bias, **kw)
+    wp = split3_weight_cached(w)
+    return None if wp is None else gemm_split3_bias_act(a, wp, bias, **kw)
+
+
 def gemm_bias_act(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
                   residual: Optional[torch.Tensor] = None, relu: bool = True,
                   out: Optional[torch.Tensor] = None,
-                  a_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  a_bias: Optional[torch.Tensor] = None, h2: bool = False) -> torch.Tensor:
     """act(a @ w.T + bias (+ residual)) in one GEMM launch: a [M,K], w [N,K], bias [N],
     residual / out [M,N], all fp32 contiguous.  From K = SPLIT3_MIN_K (N a multiple
     of 64) on the bf16 matrix cores at fp32 accuracy (gemm_split3_bias_act, the
     weight's split image cached per tensor); otherwise vd_gemm_bias_act (hipBLASLt
     with the epilogue fused, or the hand-written fp32 MFMA kernel where it is
-    faster).  a_bias [K]: a enters as relu(a + a_bias) (fused into the split GEMM's A
+    faster).  h2: the split GEMM on the two-piece fp16 scheme where h2_route serves the
+    shape (the engine's layers ask for it; activations within gemm_h2_bias_act's input
+    contract).  a_bias [K]: a enters as relu(a + a_bias) (fused into the split GEMM's A
     load; a separate pass before the other kernels).  Returns None when nothing serves
     the shape (the caller falls back, a_bias not applied)."""
     a_ = _need(a, "a")
@@ -610,10 +650,10 @@ def gemm_bias_act(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
     elif tuple(out.shape) != (M, N) or not out.is_contiguous():
         raise ValueError("out must be a contiguous %s tensor" % ((M, N),))
     if K >= SPLIT3_MIN_K and N % 64 == 0 and K % 16 == 0 and M > 0 and split3_enabled():
-        wp = split3_weight_cached(w if w.is_contiguous() else w_)
-        if wp is not None:
-            return gemm_split3_bias_act(a_, wp, b_, residual=r_, relu=relu, out=out,
-                                        a_bias=a_bias)
+        y = split_gemm_bias_act(a_, w if w.is_contiguous() else w_, b_, h2=h2, residual=r_,
+                                relu=relu, out=out, a_bias=a_bias)
+        if y is not None:
+            return y
     if a_bias is not None:
         a_ = torch.relu(a_ + _need(a_bias, "a_bias"))
     if os.environ.get("VOSDET_GEMM_TRACE") == "1":  # research: the fp32-kernel GEMMs
@@ -661,16 +701,55 @@ def gemm_split3_bias_act(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor,
     With a2 [M, K2]: w's last K2 input channels multiply a2 (a is [M, K - K2]): two
     1x1 convs of two inputs summed in one GEMM.  With a_bias [K - K2]: a enters as
     relu(a + a_bias) (the producing layer's bias + ReLU, fused into the A load)."""
+    return _split_gemm("vd_gemm_split3_bias_act", wp.split3_shape, a, wp, bias, residual, relu,
+                       out, cfg, up_hw, sub_hw, a2, a_bias)
+
+
+def gemm_h2_weight(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """W [N, K] fp32 -> the image vd_gemm_h2_bias_act reads (once per weight): the three
+    fp16 images Wm, Wr, W0 of the row-scaled weight in the kernel's fragment order
+    (N * K * 6 bytes), then the N fp32 row scales 1 / (2^11 r_n).  None when the shape is
+    not served (K a multiple of 16, N of 64)."""
+    w_ = _need(w.reshape(w.shape[0], -1), "w")
+    N, K = w_.shape
+    nbytes = lib().vd_gemm_h2_weight_size(N, K)
+    if not nbytes:
+        return None
+    wp = torch.empty(nbytes, dtype=torch.uint8, device=w_.device)
+    check(lib().vd_gemm_h2_weight(w_.data_ptr(), N, K, wp.data_ptr(), _stream()),
+          "vd_gemm_h2_weight")
+    wp.h2_shape = (N, K)
+    return wp
+
+
+def gemm_h2_bias_act(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor,
+                     residual: Optional[torch.Tensor] = None, relu: bool = True,
+                     out: Optional[torch.Tensor] = None, cfg: int = 0,
+                     up_hw: Optional[Sequence[int]] = None,
+                     sub_hw: Optional[Sequence[int]] = None,
+                     a2: Optional[torch.Tensor] = None,
+                     a_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_split3_bias_act with three fp16 products per fp32 product instead of six
+    bf16 ones (vd_gemm_h2_bias_act; wp from gemm_h2_weight): a = a0 + a1 / 2^11 in two
+    fp16 pieces, the row-scaled weight in three fp16 images, one accumulator.  Same
+    arguments.  At fp32's error level for activations whose largest magnitude lies in
+    [2^-10, 65504]; a larger activation gives a non-finite output row (include/vosdet.h)."""
+    return _split_gemm("vd_gemm_h2_bias_act", wp.h2_shape, a, wp, bias, residual, relu, out,
+                       cfg, up_hw, sub_hw, a2, a_bias)
+
+
+def _split_gemm(entry, shape, a, wp, bias, residual, relu, out, cfg, up_hw, sub_hw, a2, a_bias):
+    """The argument checks and the launch of gemm_split3_bias_act / gemm_h2_bias_act."""
     a_ = _need(a, "a")
-    N, K = wp.split3_shape
+    N, K = shape
     M = a_.shape[0]
     K2, a2_ = 0, None
     if a2 is not None:
         a2_ = _need(a2, "a2")
         K2 = a2_.shape[1]
         if a2_.shape[0] != M or a_.shape[1] + K2 != K or K2 % 16 or sub_hw is not None:
-            raise ValueError("gemm_split3_bias_act: a %s + a2 %s vs w (%d, %d)"
-                             % (tuple(a_.shape), tuple(a2_.shape), N, K))
+            raise ValueError("%s: a %s + a2 %s vs w (%d, %d)"
+                             % (entry[3:], tuple(a_.shape), tuple(a2_.shape), N, K))
     sh = sw = 0
     if sub_hw is not None:
         sh, sw = int(sub_hw[0]), int(sub_hw[1])
@@ -679,8 +758,8 @@ def gemm_split3_bias_act(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor,
         M = M // (sh * sw) * ((sh + 1) // 2) * ((sw + 1) // 2)
     b_ = _need(bias, "bias")
     if a_.dim() != 2 or a_.shape[1] + K2 != K or b_.numel() != N:
-        raise ValueError("gemm_split3_bias_act: a %s, w (%d, %d), bias %s"
-                         % (tuple(a_.shape), N, K, tuple(b_.shape)))
+        raise ValueError("%s: a %s, w (%d, %d), bias %s"
+                         % (entry[3:], tuple(a_.shape), N, K, tuple(b_.shape)))
     ab_ = None
     if a_bias is not None:
         ab_ = _need(a_bias, "a_bias")
@@ -702,13 +781,13 @@ def gemm_split3_bias_act(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor,
         out = torch.empty((M, N), dtype=torch.float32, device=a_.device)
     elif tuple(out.shape) != (M, N) or not out.is_contiguous():
         raise ValueError("out must be a contiguous %s tensor" % ((M, N),))
-    check(lib().vd_gemm_split3_bias_act(a_.data_ptr(), M, K,
-                                        a2_.data_ptr() if a2_ is not None else None, K2,
-                                        ab_.data_ptr() if ab_ is not None else None,
-                                        wp.data_ptr(), N, b_.data_ptr(),
-                                        r_.data_ptr() if r_ is not None else None, uh, uw,
-                                        sh, sw, int(relu), out.data_ptr(), int(cfg), _stream()),
-          "vd_gemm_split3_bias_act")
+    check(getattr(lib(), entry)(a_.data_ptr(), M, K,
+                                a2_.data_ptr() if a2_ is not None else None, K2,
+                                ab_.data_ptr() if ab_ is not None else None,
+                                wp.data_ptr(), N, b_.data_ptr(),
+                                r_.data_ptr() if r_ is not None else None, uh, uw,
+                                sh, sw, int(relu), out.data_ptr(), int(cfg), _stream()),
+          entry)
     return out
 
 
@@ -719,23 +798,27 @@ def mask_head_upconv_logits(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tenso
     split-bf16 launch (vd_mask_head_upconv_logits): x [R P P, 256] NHWC RoI map rows,
     wp = gemm_split3_weight of the upconv weight as [(i, j, co), 256], bias [1024],
     cls_w [classes, 256], cls_b [classes], roi_ch [R] (int32 class channels).  Returns
-    [R, 2P, 2P] mask probabilities."""
+    [R, 2P, 2P] mask probabilities.  A wp from gemm_h2_weight runs the two-piece fp16
+    scheme (vd_mask_head_upconv_logits_h2)."""
     x_ = _need(x, "x")
     R = int(roi_ch.numel())
-    if x_.dim() != 2 or x_.shape[0] != R * P * P or tuple(wp.split3_shape) != (1024, x_.shape[1]):
+    h2 = hasattr(wp, "h2_shape")
+    shape = wp.h2_shape if h2 else wp.split3_shape
+    entry = "vd_mask_head_upconv_logits_h2" if h2 else "vd_mask_head_upconv_logits"
+    if x_.dim() != 2 or x_.shape[0] != R * P * P or tuple(shape) != (1024, x_.shape[1]):
         raise ValueError("mask_head_upconv_logits: x %s, %d RoIs of %d x %d, w %s"
-                         % (tuple(x_.shape), R, P, P, wp.split3_shape))
+                         % (tuple(x_.shape), R, P, P, shape))
     cw = _need(cls_w, "cls_w")
     if cw.dim() != 2 or cw.shape[1] != 256:
         raise ValueError("cls_w must be [classes, 256], got %s" % (tuple(cw.shape),))
     ch = _need(roi_ch, "roi_ch", torch.int32)
     if out is None:
         out = torch.empty((R, 2 * P, 2 * P), dtype=torch.float32, device=x_.device)
-    check(lib().vd_mask_head_upconv_logits(x_.data_ptr(), x_.shape[0], x_.shape[1], wp.data_ptr(),
-                                           _need(bias, "bias").data_ptr(), cw.data_ptr(),
-                                           _need(cls_b, "cls_b").data_ptr(), ch.data_ptr(), P,
-                                           out.data_ptr(), _stream()),
-          "vd_mask_head_upconv_logits")
+    check(getattr(lib(), entry)(x_.data_ptr(), x_.shape[0], x_.shape[1], wp.data_ptr(),
+                                _need(bias, "bias").data_ptr(), cw.data_ptr(),
+                                _need(cls_b, "cls_b").data_ptr(), ch.data_ptr(), P,
+                                out.data_ptr(), _stream()),
+          entry)
     return out
 
 
