@@ -177,10 +177,12 @@ int launch_flow_align_bwd(const float *top_diff, const float *feat, const float 
 // Statistics: ws[set][n][g] = {sum, sum of squares} (double) of x (+ x2) over
 // the group's C/G channels x H*W pixels.  Up to 3 independent tensors per
 // launch (blockIdx.z = set): the ConvGRU's update and reset gates share one.
-// NHWC, C % 4 == 0, C <= 1024, G <= 64.  Thread t owns channel quad t % C4 of
-// pixels t / C4, t / C4 + ppi, ...; the four lanes of its quad are summed
-// separately and folded into their groups at the end, so any C / G works
-// (the GN ResNet's 64-channel stages have 2 channels per group).
+// NHWC, C % 4 == 0, G <= 64; any C: the q0 loop walks the C / 4 channel quads in
+// blocks of 256 (res5's C = 2048 takes two passes at one pixel per iteration).
+// Within a pass thread t owns channel quad t % nq of pixels t / nq, t / nq + ppi,
+// ...; the four lanes of its quad are summed separately and folded into their
+// groups at the end, so any C / G works (the GN ResNet's 64-channel stages have
+// 2 channels per group, a quad then straddles two groups).
 __global__ __launch_bounds__(256) void gn_stats_nhwc_kernel(GnSets sets, int HW, int C, int G,
                                                             int pix_per_block) {
     __shared__ double red[2][64];  // per group (G <= 64)
