@@ -907,6 +907,68 @@ int vd_nms_oks_frames(const float *keyps, int64_t keyps_rows, int K, const float
 int vd_compute_oks(const float *src_keypoints, const float *src_roi, const float *dst_keypoints,
                    int N, int K, double *out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Test-time augmentation (TEST.BBOX_AUG / TEST.MASK_AUG) with the UNION box
+ * heuristics: im_detect_bbox_aug (lib/core/test.py:193-311; flip_boxes,
+ * lib/utils/boxes.py:261-266) followed by box_results_with_nms_and_limit on the
+ * np.vstack of the views' scores and boxes, and im_detect_mask_aug's combination
+ * (test.py:405-476).  Stream-ordered, no allocation, no host read.
+ *
+ * The union's per-class candidate lists live in the workspace (cand_cap rows per
+ * (image, class), cand_cap <= 16384, VD_ERR_SHAPE beyond):
+ *   vd_box_union_workspace_size = 2 * al(20 S c) + al(4 S c) + al(S c) + 2 * al(4 S)
+ *   + al(4 F) bytes with S = num_images * num_classes, c = cand_cap, F = num_images and
+ *   al() rounding up to 256: about 45 bytes per (image, class, row), no quadratic term.
+ *
+ * vd_box_union_add_view: once per box view, in np.vstack order (test.py:218-261:
+ * the flipped view, the scales, the identity view last); first != 0 on the first
+ * view of a step empties the lists.  rois / cls_prob / bbox_pred / roi_count are the
+ * view's, as for vd_box_detections; im_scale[i] the view's scale, im_hw[i] the
+ * original frame.  Per (image, class j >= 1) the rows with cls_prob >= score_thresh
+ * are decoded and clipped as vd_box_detections does, a flipped view's (hflip != 0)
+ * then mapped back with flip_boxes in float32 (x1' = (W - x2) - 1, x2' = (W - x1) -
+ * 1), and appended in row order behind the earlier views' rows.  A list that would
+ * exceed cand_cap, or a negative roi_count, fails the image.
+ *
+ * vd_box_union_detections: per (image, class) the list sorted by (score
+ * descending, higher vstack index first), greedy NMS at any length without an
+ * n x n mask, TEST.SOFT_NMS / TEST.BBOX_VOTE as vd_box_detections_ex (voters: all
+ * of the class's candidates; soft-NMS needs cand_cap <= 4096, VD_ERR_SHAPE beyond),
+ * then the detections limit: dets_out / det_cls_out / det_count_out as
+ * vd_box_detections writes them, rows ordered by class then vstack index.  A failed
+ * image gets count -1.  cand_count_out (may be NULL): [num_images][num_classes]
+ * int32, the lengths of the lists. */
+size_t vd_box_union_workspace_size(int cand_cap, int num_images, int num_classes);
+int vd_box_union_add_view(const float *rois, const float *cls_prob, const float *bbox_pred,
+                          const int32_t *roi_count, int R_cap, int num_images, int num_classes,
+                          const float *im_scale, const int32_t *im_hw, int hflip, int first,
+                          float score_thresh, const float *bbox_reg_weights, int cand_cap,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int vd_box_union_detections(int cand_cap, int num_images, int num_classes, float nms_thresh,
+                            int dets_per_im, int soft_nms_method, float soft_nms_sigma,
+                            float soft_nms_min_score, int bbox_vote_method,
+                            float bbox_vote_thresh, float bbox_vote_beta, int det_cap,
+                            float *dets_out, int32_t *det_cls_out, int32_t *det_count_out,
+                            int32_t *cand_count_out, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
+/* TEST.MASK_AUG.HEUR (test.py:459-474).  vd_mask_aug_accumulate folds one view's
+ * class-selected masks [M, R, R] (sigmoid outputs) into acc [M, R, R], once per
+ * mask view in masks_ts order (the identity view first; first != 0 there); a
+ * flipped view (hflip != 0) is read with its last axis reversed (test.py:491).
+ *   SOFT_AVG   acc += y (float32, view order)        finish: acc / float(T)
+ *   SOFT_MAX   acc = max(acc, y)                     finish: nothing
+ *   LOGIT_AVG  acc += -1 * log((1 - y) / max(y, 1e-20))
+ *                                                    finish: 1 / (1 + exp(-acc / T))
+ * SOFT_AVG and SOFT_MAX equal numpy's np.mean / np.amax bit for bit; LOGIT_AVG
+ * differs by the device's logf / expf rounding. */
+#define VD_MASK_AUG_SOFT_AVG 0
+#define VD_MASK_AUG_SOFT_MAX 1
+#define VD_MASK_AUG_LOGIT_AVG 2
+int vd_mask_aug_accumulate(float *acc, const float *masks, int M, int R, int hflip, int heur,
+                           int first, void *stream);
+int vd_mask_aug_finish(float *acc, int M, int R, int T, int heur, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,14 @@ SIGNATURES = {
                                _P, _P, _S, _P]),
     "vd_box_detections_ex": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _P,
                                   _I, _F, _F, _I, _F, _F, _I, _P, _P, _P, _P, _S, _P]),
+    # test-time augmentation: the box views' union, the mask heuristics
+    "vd_box_union_workspace_size": (_S, [_I, _I, _I]),
+    "vd_box_union_add_view": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P,
+                                   _S, _P]),
+    "vd_box_union_detections": (_I, [_I, _I, _I, _F, _I, _I, _F, _F, _I, _F, _F, _I, _P, _P, _P,
+                                     _P, _P, _S, _P]),
+    "vd_mask_aug_accumulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "vd_mask_aug_finish": (_I, [_P, _I, _I, _I, _I, _P]),
     "vd_stem_weight_size": (_S, []),
     "vd_stem_weight_pack": (_I, [_P, _P, _P]),
     "vd_stem_conv_pool": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),

@@ -38,6 +38,17 @@ def nms(dets, thresh):
     return ops.nms(t, thresh).cpu().numpy()
 
 
+def flip_boxes(boxes, im_width):
+    """Flip boxes horizontally (lib/utils/boxes.py:261-266): an (N, 4k) ndarray, or a
+    tensor on any device; the arithmetic stays in the boxes' dtype (float32 boxes:
+    x1' = (W - x2) - 1 in float32, what the device kernels of the test-time
+    augmentation compute)."""
+    flipped = boxes.clone() if isinstance(boxes, torch.Tensor) else boxes.copy()
+    flipped[:, 0::4] = im_width - boxes[:, 2::4] - 1
+    flipped[:, 2::4] = im_width - boxes[:, 0::4] - 1
+    return flipped
+
+
 def _dev(d):
     return torch.from_numpy(np.ascontiguousarray(d, np.float32)).to(
         torch.device("cuda", torch.cuda.current_device()))

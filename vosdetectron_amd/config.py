@@ -84,9 +84,16 @@ def default_cfg() -> AttrDict:
             SOFT_NMS=_d(ENABLED=False, METHOD="linear", SIGMA=0.5),
             BBOX_VOTE=_d(ENABLED=False, VOTE_TH=0.8, SCORING_METHOD="ID",
                          SCORING_METHOD_BETA=1.0),
+            # config.py:246-316: test-time augmentation, accepted by load_cfg(test_aug=True)
+            # only (engine.AugFramePipeline); aug_views() lists the views
+            BBOX_AUG=_d(ENABLED=False, SCORE_HEUR="UNION", COORD_HEUR="UNION", H_FLIP=False,
+                        SCALES=(), MAX_SIZE=4000, SCALE_H_FLIP=False, SCALE_SIZE_DEP=False,
+                        ASPECT_RATIOS=(), ASPECT_RATIO_H_FLIP=False),
+            MASK_AUG=_d(ENABLED=False, HEUR="SOFT_AVG", H_FLIP=False, SCALES=(), MAX_SIZE=4000,
+                        SCALE_H_FLIP=False, SCALE_SIZE_DEP=False, ASPECT_RATIOS=(),
+                        ASPECT_RATIO_H_FLIP=False),
             # inference options read only to be rejected when enabled (UNSUPPORTED)
             # (NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU below are built: VOSPipeline)
-            BBOX_AUG=_d(ENABLED=False), MASK_AUG=_d(ENABLED=False),  # config.py:246-316
             KPS_AUG=_d(ENABLED=False),  # config.py:322-351
             NMS_WITH_MASK_IOU=0., NMS_SMALL_BOX_IOU=0.,  # config.py:951-953: the VOS
             NMS_SMALL_BOX_SCORE_THRESHOLD=0.),  # loop's heuristics (engine.VOSPipeline)
@@ -151,8 +158,10 @@ UNSUPPORTED = (
      "box-voting scoring TEMP_AVG (numpy float32 log / exp), lib/utils/boxes.py:300-320"),
     ("TEST.SOFT_NMS", lambda v: bool(v.get("ENABLED")) and v.get("METHOD") not in (
         "hard", "linear", "gaussian"), "soft-NMS method (boxes.py:344 asserts)"),
-    ("TEST.BBOX_AUG.ENABLED", bool, "box test-time augmentation, lib/core/test.py:193-727"),
-    ("TEST.MASK_AUG.ENABLED", bool, "mask test-time augmentation, lib/core/test.py:405-480"),
+    ("TEST.BBOX_AUG.ENABLED", bool, "box test-time augmentation, lib/core/test.py:193-363, as "
+     "a config key: load_cfg(..., test_aug=True) accepts it for engine.AugFramePipeline"),
+    ("TEST.MASK_AUG.ENABLED", bool, "mask test-time augmentation, lib/core/test.py:405-526, as "
+     "a config key: load_cfg(..., test_aug=True) accepts it for engine.AugFramePipeline"),
     ("TEST.KPS_AUG.ENABLED", bool, "keypoint test-time augmentation (keypoint heads out of scope)"),
     ("MODEL.USE_DELTA_FLOW", _WithCfg(lambda v, c: bool(v) and not c.get("VOS", False)),
      "delta-flow head on a model other than Generalized_VOS_RCNN: only the VOS builder has it, "
@@ -178,10 +187,46 @@ def _get(cfg, key):
     return cfg
 
 
-def check_supported(cfg) -> None:
-    """Raise NotImplementedError naming every enabled option of ``UNSUPPORTED``."""
+TEST_AUG_KEYS = ("TEST.BBOX_AUG.ENABLED", "TEST.MASK_AUG.ENABLED")
+MASK_AUG_HEURS = ("SOFT_AVG", "SOFT_MAX", "LOGIT_AVG")
+
+
+def _aug_on(aug):
+    return lambda v, c: bool(c.TEST[aug].ENABLED) and bool(v)
+
+
+def _aug_not(aug, allowed):
+    return lambda v, c: bool(c.TEST[aug].ENABLED) and v not in allowed
+
+
+# What load_cfg(test_aug=True) still refuses of an enabled TEST.BBOX_AUG / MASK_AUG.
+UNSUPPORTED_TEST_AUG = tuple(
+    (key, _WithCfg(pred), where) for key, pred, where in (
+        ("TEST.BBOX_AUG.ASPECT_RATIOS", _aug_on("BBOX_AUG"),
+         "aspect-ratio views need an anisotropic resize, lib/core/test.py:330-363"),
+        ("TEST.MASK_AUG.ASPECT_RATIOS", _aug_on("MASK_AUG"),
+         "aspect-ratio views need an anisotropic resize, lib/core/test.py:509-526"),
+        ("TEST.BBOX_AUG.SCALE_SIZE_DEP", _aug_on("BBOX_AUG"),
+         "the reference asserts it off, lib/core/test.py:197"),
+        ("TEST.MASK_AUG.SCALE_SIZE_DEP", _aug_on("MASK_AUG"),
+         "the reference asserts it off, lib/core/test.py:418"),
+        ("TEST.BBOX_AUG.SCORE_HEUR", _aug_not("BBOX_AUG", ("UNION",)),
+         "the reference asserts UNION for Faster R-CNN models, lib/core/test.py:205-207"),
+        ("TEST.BBOX_AUG.COORD_HEUR", _aug_not("BBOX_AUG", ("UNION",)),
+         "UNION whenever the score heuristic is, lib/core/test.py:199-201"),
+        ("TEST.MASK_AUG.HEUR", _aug_not("MASK_AUG", MASK_AUG_HEURS),
+         "the reference raises, lib/core/test.py:471-474"),
+    ))
+
+
+def check_supported(cfg, test_aug: bool = False) -> None:
+    """Raise NotImplementedError naming every enabled option of ``UNSUPPORTED``;
+    test_aug accepts TEST.BBOX_AUG / TEST.MASK_AUG but for ``UNSUPPORTED_TEST_AUG``."""
     bad = []
-    for key, enabled, where in UNSUPPORTED:
+    table = UNSUPPORTED
+    if test_aug:
+        table = tuple(r for r in UNSUPPORTED if r[0] not in TEST_AUG_KEYS) + UNSUPPORTED_TEST_AUG
+    for key, enabled, where in table:
         try:
             v = _get(cfg, key)
         except (KeyError, TypeError):
@@ -193,9 +238,37 @@ def check_supported(cfg) -> None:
                                   + "; ".join(bad))
 
 
-def load_cfg(path: str | None = None, overrides: dict | None = None) -> AttrDict:
+def aug_views(cfg):
+    """The views of im_detect_bbox_aug / im_detect_mask_aug as two ordered lists of
+    (scale, max_size, hflip).  Box views in np.vstack order (lib/core/test.py:218-261):
+    the flipped view at (TEST.SCALE, TEST.MAX_SIZE), each BBOX_AUG.SCALES entry (then
+    its flip with SCALE_H_FLIP), the identity view LAST.  Mask views in masks_ts order
+    (test.py:425-445): the identity view FIRST, the flipped view, the scales.  With an
+    AUG key off its list is the identity view alone."""
+    tst = cfg.TEST
+    ident = (tst.SCALE, tst.MAX_SIZE, False)
+
+    def extra(aug):
+        v = []
+        if aug.H_FLIP:
+            v.append((tst.SCALE, tst.MAX_SIZE, True))
+        for s in aug.SCALES:
+            v.append((s, aug.MAX_SIZE, False))
+            if aug.SCALE_H_FLIP:
+                v.append((s, aug.MAX_SIZE, True))
+        return v
+
+    box = (extra(tst.BBOX_AUG) if tst.BBOX_AUG.ENABLED else []) + [ident]
+    mask = [ident] + (extra(tst.MASK_AUG) if tst.MASK_AUG.ENABLED else [])
+    return box, mask
+
+
+def load_cfg(path: str | None = None, overrides: dict | None = None,
+             test_aug: bool = False) -> AttrDict:
     """Defaults, then a reference YAML (safe loader), then dotted overrides.
-    Raises NotImplementedError if the result enables an ``UNSUPPORTED`` option."""
+    Raises NotImplementedError if the result enables an ``UNSUPPORTED`` option.
+    test_aug=True accepts TEST.BBOX_AUG.ENABLED / TEST.MASK_AUG.ENABLED (the config
+    runs on engine.AugFramePipeline only) and refuses ``UNSUPPORTED_TEST_AUG``."""
     cfg = default_cfg()
     if path:
         with open(path) as f:
@@ -206,7 +279,7 @@ def load_cfg(path: str | None = None, overrides: dict | None = None) -> AttrDict
         for p in parts[:-1]:
             d = d[p]
         d[parts[-1]] = val
-    check_supported(cfg)
+    check_supported(cfg, test_aug)
     return cfg
 
 

@@ -792,6 +792,52 @@ int vd_detections_postfilter(float *dets, int32_t *classes, int32_t *counts, int
                                         VD_STREAM(stream));
 }
 
+size_t vd_box_union_workspace_size(int cand_cap, int num_images, int num_classes) {
+    if (cand_cap < 1 || num_images < 1 || num_classes < 1) return 0;
+    return box_union_workspace_bytes(cand_cap, num_images, num_classes);
+}
+
+int vd_box_union_add_view(const float *rois, const float *cls_prob, const float *bbox_pred,
+                          const int32_t *roi_count, int R_cap, int num_images, int num_classes,
+                          const float *im_scale, const int32_t *im_hw, int hflip, int first,
+                          float score_thresh, const float *bbox_reg_weights, int cand_cap,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+    if (!rois || !cls_prob || !bbox_pred || !roi_count || !im_scale || !im_hw ||
+        !bbox_reg_weights)
+        return VD_ERR_ARG;
+    return launch_box_union_add_view(rois, cls_prob, bbox_pred, roi_count, R_cap, num_images,
+                                     num_classes, im_scale, im_hw, hflip, first, score_thresh,
+                                     bbox_reg_weights, cand_cap, workspace, workspace_bytes,
+                                     VD_STREAM(stream));
+}
+
+int vd_box_union_detections(int cand_cap, int num_images, int num_classes, float nms_thresh,
+                            int dets_per_im, int soft_nms_method, float soft_nms_sigma,
+                            float soft_nms_min_score, int bbox_vote_method,
+                            float bbox_vote_thresh, float bbox_vote_beta, int det_cap,
+                            float *dets_out, int32_t *det_cls_out, int32_t *det_count_out,
+                            int32_t *cand_count_out, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+    if (!dets_out || !det_cls_out || !det_count_out) return VD_ERR_ARG;
+    return launch_box_union_detections(cand_cap, num_images, num_classes, nms_thresh, dets_per_im,
+                                       soft_nms_method, soft_nms_sigma, soft_nms_min_score,
+                                       bbox_vote_method, bbox_vote_thresh, bbox_vote_beta,
+                                       det_cap, dets_out, det_cls_out, det_count_out,
+                                       cand_count_out, workspace, workspace_bytes,
+                                       VD_STREAM(stream));
+}
+
+int vd_mask_aug_accumulate(float *acc, const float *masks, int M, int R, int hflip, int heur,
+                           int first, void *stream) {
+    if (M > 0 && (!acc || !masks)) return VD_ERR_ARG;
+    return launch_mask_aug_accumulate(acc, masks, M, R, hflip, heur, first, VD_STREAM(stream));
+}
+
+int vd_mask_aug_finish(float *acc, int M, int R, int T, int heur, void *stream) {
+    if (M > 0 && !acc) return VD_ERR_ARG;
+    return launch_mask_aug_finish(acc, M, R, T, heur, VD_STREAM(stream));
+}
+
 size_t vd_mask_iou_nms_workspace_size(int n, int im_h, int im_w) {
     return mask_iou_nms_workspace_bytes(n, im_h, im_w);
 }

@@ -253,4 +253,22 @@ int launch_detections_postfilter(float *dets, int32_t *cls, int32_t *counts, int
                                  int det_cap, float nms_cross_class, int num_det_per_class_pre,
                                  hipStream_t s);
 
+// test-time augmentation: the UNION of the box views (box_union.hip), the mask
+// heuristics (mask_aug.hip)
+size_t box_union_workspace_bytes(int cand_cap, int num_images, int num_classes);
+int launch_box_union_add_view(const float *rois, const float *cls_prob, const float *bbox_pred,
+                              const int32_t *roi_count, int R_cap, int num_images, int K,
+                              const float *im_scale, const int32_t *im_hw, int hflip, int first,
+                              float score_thresh, const float *bbox_weights, int cand_cap,
+                              void *workspace, size_t ws_bytes, hipStream_t s);
+int launch_box_union_detections(int cand_cap, int num_images, int K, float nms_thresh,
+                                int dets_per_im, int soft_method, float soft_sigma, float soft_min,
+                                int vote_method, float vote_th, float vote_beta, int det_cap,
+                                float *dets_out, int32_t *det_cls_out, int32_t *det_count_out,
+                                int32_t *cand_count_out, void *workspace, size_t ws_bytes,
+                                hipStream_t s);
+int launch_mask_aug_accumulate(float *acc, const float *masks, int M, int R, int hflip, int heur,
+                               int first, hipStream_t s);
+int launch_mask_aug_finish(float *acc, int M, int R, int T, int heur, hipStream_t s);
+
 }  // namespace vd

@@ -96,6 +96,12 @@ class FramePipeline:
                 "%s: MODEL.KEYPOINTS_ON configs run on KeypointFramePipeline (FPN, frames of "
                 "one size); ragged, C4 and VOS keypoint steps are not built"
                 % type(self).__name__)
+        if (cfg.TEST.BBOX_AUG.ENABLED or cfg.TEST.MASK_AUG.ENABLED) \
+                and not isinstance(self, AugFramePipeline):
+            raise NotImplementedError(
+                "%s: TEST.BBOX_AUG / TEST.MASK_AUG run on AugFramePipeline (FPN mask configs, "
+                "frames of one size); ragged, C4, VOS and keypoint steps with test-time "
+                "augmentation are not built" % type(self).__name__)
         if not cfg.MODEL.KEYPOINTS_ON and not hasattr(model, "Mask_Head"):
             raise NotImplementedError(
                 "%s: the model has no Mask_Head (MODEL.MASK_ON False); a box-only step is "
@@ -202,6 +208,34 @@ class FramePipeline:
         F, im_info, im_scale_t, im_scale_d, im_hw = self._frame_rows(frames)
         feats = self.backbone(frames)
         self._mark("conv_body")
+        tst = cfg.TEST
+        rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post = \
+            self._box_stages(feats, im_info)
+        K = cls_prob.shape[1]
+        bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
+        dets, dcls, dcnt = ops.box_detections(
+            rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
+            im_scale_t, im_hw, tst.SCORE_THRESH, tst.NMS,
+            tst.DETECTIONS_PER_IM, cfg.MODEL.BBOX_REG_WEIGHTS, self.det_cap,
+            nms_cross_class=tst.NMS_CROSS_CLASS, num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE,
+            **self._nms_options)
+        self._post_detections(dets, dcls, dcnt)
+        self._mark("misc_bbox")
+        out = {"dets": dets, "classes": dcls, "counts": dcnt, "rois": rois, "roi_counts": rcnt,
+               "cls_prob": cls_prob, "bbox_pred": bbox_pred}
+        if keep_intermediates:  # for stage-wise parity tests
+            out.update(feats=feats, rpn_probs=probs, rpn_deltas=deltas, pyramid=pyr)
+        self._roi_heads(out, F, pyr, fast, im_scale_d, keep_intermediates)
+        if sync:
+            self.complete(out)
+        return out
+
+    def _box_stages(self, feats, im_info):
+        """im_detect_bbox's stages between the body and the decode, for the frames
+        whose blob geometry im_info holds: RPN heads, proposals, collect, box RoIAlign
+        and the box head.  -> (rois, roi counts, cls_prob, bbox_pred (as Box_Outs
+        returns it), RPN probs, RPN deltas, NHWC pyramid, fast, post)."""
+        cfg = self.cfg
         # RPN heads on P2..P6 (finest first for the proposal kernel)
         probs, deltas = [], []
         for lvl in self.rpn_levels:
@@ -228,24 +262,7 @@ class FramePipeline:
         x = self.model.Box_Head.mlp_nhwc(box_feat) if fast else self.model.Box_Head.mlp(box_feat)
         cls_prob, bbox_pred = self.model.Box_Outs(x)
         self._mark("box_head")
-        K = cls_prob.shape[1]
-        bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
-        dets, dcls, dcnt = ops.box_detections(
-            rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
-            im_scale_t, im_hw, tst.SCORE_THRESH, tst.NMS,
-            tst.DETECTIONS_PER_IM, cfg.MODEL.BBOX_REG_WEIGHTS, self.det_cap,
-            nms_cross_class=tst.NMS_CROSS_CLASS, num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE,
-            **self._nms_options)
-        self._post_detections(dets, dcls, dcnt)
-        self._mark("misc_bbox")
-        out = {"dets": dets, "classes": dcls, "counts": dcnt, "rois": rois, "roi_counts": rcnt,
-               "cls_prob": cls_prob, "bbox_pred": bbox_pred}
-        if keep_intermediates:  # for stage-wise parity tests
-            out.update(feats=feats, rpn_probs=probs, rpn_deltas=deltas, pyramid=pyr)
-        self._roi_heads(out, F, pyr, fast, im_scale_d, keep_intermediates)
-        if sync:
-            self.complete(out)
-        return out
+        return rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post
 
     def _roi_heads(self, out, F, pyr, fast, im_scale_d, keep_intermediates):
         """The per-detection heads after misc_bbox: here im_detect_mask."""
@@ -494,6 +511,217 @@ def frame_keypoints(pipe: "KeypointFramePipeline", out: dict, num_classes: int =
         res.append(cls_keyps)
         start += k
     return res
+
+
+class _ViewGeom:
+    """Blob geometry of one test-time-augmentation view (scale, max_size, hflip) for
+    frames of one size: FramePipeline's per-frame rows at that view's scale."""
+
+    def __init__(self, view, H, W, stride, F, device):
+        self.view = view
+        self.hflip = bool(view[2])
+        self.scale = ops.target_scale(H, W, view[0], view[1])
+        self.Hr, self.Wr = ops.resized_hw(H, W, self.scale)
+        self.Hp = int(math.ceil(self.Hr / stride) * stride)
+        self.Wp = int(math.ceil(self.Wr / stride) * stride)
+        self.im_info = torch.tensor([[self.Hp, self.Wp, self.scale]] * F, dtype=torch.float32,
+                                    device=device)
+        self.im_scale_t = torch.full((F,), self.scale, dtype=torch.float32, device=device)
+        self.im_scale_d = torch.full((F,), self.scale, dtype=torch.float64, device=device)
+
+
+class AugFramePipeline(FramePipeline):
+    """FramePipeline with the reference's test-time augmentation (TEST.BBOX_AUG /
+    TEST.MASK_AUG, lib/core/test.py:193-363, 405-526) for the FPN mask configs and
+    frames of one size; cfg comes from config.load_cfg(..., test_aug=True).
+
+      per distinct view (config.aug_views: scale, max_size, hflip), on the frames or
+      their horizontal flip: blob at the view's geometry --> body --> [box views: RPN,
+      proposals, collect, box RoIAlign, box head --> vd_box_union_add_view in np.vstack
+      order, the identity view last]
+      --> vd_box_union_detections (UNION heuristics: one box_results_with_nms_and_limit
+      over every view's rows) --> vd_detections_postfilter
+      --> per mask view, the identity view first: the final detections (flip_boxes for a
+      flipped view) --> vd_mask_rois at the view's scale --> mask RoIAlign + mask head on
+      the view's pyramid --> vd_mask_aug_accumulate --> vd_mask_aug_finish.
+
+    The reference runs the body again for every mask view; here a view's pyramid is kept
+    from the box pass to the mask pass (pyramid_budget_bytes bounds batch x the kept
+    pyramids).  cand_cap: rows of a class's candidate list per image (default min(16384,
+    box views x post_nms_topN)); an image whose list overflows fails at complete().
+    The result dict is FramePipeline's: masks are the combined masks, mask_rois /
+    mask_feat the identity view's.  keep_intermediates adds out["views"]: per distinct
+    view a dict with rois, roi_counts, cls_prob, bbox_pred, pyramid and blob (box views)
+    and mask_rois, masks (mask views), and out["cand_counts"] [F,K]."""
+
+    def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
+                 det_cap=256, device="cuda", cand_cap=None, pyramid_budget_bytes=24 << 30):
+        from . import config as vcfg
+        if not cfg.FPN.FPN_ON or bool(cfg.get("VOS", False)) or cfg.MODEL.KEYPOINTS_ON:
+            raise NotImplementedError(
+                "AugFramePipeline: FPN mask configs only (test-time augmentation on the C4, "
+                "VOS and keypoint pipelines is not built)")
+        vcfg.check_supported(cfg, test_aug=True)
+        super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
+        self.box_views, self.mask_views = vcfg.aug_views(cfg)
+        st = cfg.FPN.COARSEST_STRIDE
+        self.geom = {}
+        for v in self.box_views + self.mask_views:
+            if v not in self.geom:
+                self.geom[v] = _ViewGeom(v, self.H, self.W, st, batch, self.device)
+        self.mask_heur = cfg.TEST.MASK_AUG.HEUR if cfg.TEST.MASK_AUG.ENABLED else "SOFT_AVG"
+        post = int(cfg.TEST.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
+        self.cand_cap = int(cand_cap or min(ops.UNION_MAX_CAND, len(self.box_views) * post))
+        kept = sum(self.pyramid_bytes(self.geom[v]) for v in set(self.mask_views))
+        if batch * kept > pyramid_budget_bytes:
+            raise ValueError(
+                "AugFramePipeline: the %d mask views' pyramids take %d x %d bytes, over "
+                "pyramid_budget_bytes = %d (fewer frames per step, or fewer MASK_AUG views)"
+                % (len(set(self.mask_views)), batch, kept, pyramid_budget_bytes))
+        self._unions = {}
+
+    def pyramid_bytes(self, g) -> int:
+        """Bytes of one frame's RoI pyramid (P2..P5, FPN.DIM channels, fp32) at view g."""
+        n = 0
+        for lvl in self.roi_levels:
+            n += -(-g.Hp // 2 ** lvl) * -(-g.Wp // 2 ** lvl)
+        return n * int(self.cfg.FPN.DIM) * 4
+
+    def _view_blob(self, frames, g):
+        """make_blob at view g's geometry."""
+        nhwc = self.channels_last
+        if g.scale == 1.0:
+            blob = ops.image_to_blob(frames, self.lut, g.Hp, g.Wp, nhwc=nhwc)
+        else:
+            blob = ops.image_resize_to_blob(frames, self.lut, g.scale, g.Hp, g.Wp, nhwc=nhwc)
+        return blob.permute(0, 3, 1, 2) if nhwc else blob
+
+    def _union(self, F, K):
+        if (F, K) not in self._unions:
+            self._unions[(F, K)] = ops.BoxUnion(self.cand_cap, F, K, self.device)
+        return self._unions[(F, K)]
+
+    def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
+        cfg, tst = self.cfg, self.cfg.TEST
+        F = frames.shape[0]
+        im_hw = self.im_hw[:F]
+        flipped = frames.flip(2) if any(v[2] for v in self.geom) else None
+        mask_set = set(self.mask_views)
+        pyrs, views, union = {}, {}, None
+        for i, v in enumerate(self.box_views):
+            g = self.geom[v]
+            blob = self._view_blob(flipped if g.hflip else frames, g)
+            feats = self.model.Conv_Body(blob)
+            self._mark("conv_body")
+            rois, rcnt, cls_prob, bbox_pred, _, _, pyr, fast, post = \
+                self._box_stages(feats, g.im_info[:F])
+            K = cls_prob.shape[1]
+            bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
+            union = union or self._union(F, K)
+            union.add_view(rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
+                           g.im_scale_t[:F], im_hw, g.hflip, tst.SCORE_THRESH,
+                           cfg.MODEL.BBOX_REG_WEIGHTS, first=i == 0)
+            self._mark("union_add_view")
+            if v in mask_set:
+                pyrs[v] = (pyr, fast)
+            if keep_intermediates:
+                views[v] = dict(rois=rois, roi_counts=rcnt, cls_prob=cls_prob,
+                                bbox_pred=bbox_pred, pyramid=pyr, blob=blob)
+        cand = torch.zeros((F, K), dtype=torch.int32, device=self.device)
+        dets, dcls, dcnt = union.detections(
+            tst.NMS, tst.DETECTIONS_PER_IM, self.det_cap, nms_cross_class=tst.NMS_CROSS_CLASS,
+            num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE, cand_counts=cand,
+            **self._nms_options)
+        self._mark("misc_bbox")
+        ident = views.get(self.box_views[-1]) or dict(rois=rois, roi_counts=rcnt,
+                                                      cls_prob=cls_prob, bbox_pred=bbox_pred)
+        out = {"dets": dets, "classes": dcls, "counts": dcnt, "cand_counts": cand,
+               "rois": ident["rois"], "roi_counts": ident["roi_counts"],
+               "cls_prob": ident["cls_prob"], "bbox_pred": ident["bbox_pred"]}
+        # the mask-only views' bodies (the reference's im_conv_body_only)
+        for v in self.mask_views:
+            if v not in pyrs:
+                g = self.geom[v]
+                blob = self._view_blob(flipped if g.hflip else frames, g)
+                pyrs[v] = (self.nhwc_pyramid(self.model.Conv_Body(blob)),
+                           self.channels_last and getattr(self.model.Box_Head, "nhwc_ready",
+                                                          False))
+                self._mark("conv_body")
+                if keep_intermediates:
+                    views.setdefault(v, {}).update(pyramid=pyrs[v][0], blob=blob)
+        if keep_intermediates:
+            out["views"] = views
+        out["_pyrs"] = pyrs
+        out["masks"], out["mask_rois"], out["mask_feat"], out["mask_total"] = \
+            self._aug_masks(out, self.mask_rows(F), 0, views if keep_intermediates else None)
+        self._mark("im_detect_mask")
+        if sync:
+            self.complete(out)
+        return out
+
+    def _aug_masks(self, out, rows, row0, views=None):
+        """im_detect_mask_aug for rows [row0, row0 + rows) of the mask batch: every mask
+        view's masks combined by TEST.MASK_AUG.HEUR.  -> (masks, the identity view's
+        mask_rois and mask_feat, the device total)."""
+        cfg = self.cfg
+        dets, dcls, dcnt = out["dets"], out["classes"], out["counts"]
+        F = dets.shape[0]
+        dets_hf = None
+        acc = first = None
+        for i, v in enumerate(self.mask_views):
+            g = self.geom[v]
+            d = dets
+            if g.hflip:
+                if dets_hf is None:  # flip_boxes, float32: x1' = (W - x2) - 1
+                    dets_hf = dets.clone()
+                    dets_hf[..., 0] = self.W - dets[..., 2] - 1
+                    dets_hf[..., 2] = self.W - dets[..., 0] - 1
+                d = dets_hf
+            mrois, mlvl, mcls, mtotal = ops.mask_rois(
+                d, dcls, dcnt, g.im_scale_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
+                cfg.FPN.ROI_MAX_LEVEL, row0=row0)
+            pyr, fast = out["_pyrs"][v]
+            masks, mfeat = self._mask_batch(pyr, mrois, mlvl, mcls, fast)
+            masks = masks.contiguous()
+            if i == 0:
+                acc = torch.empty_like(masks)
+                first = (mrois, mfeat, mtotal)
+            ops.mask_aug_accumulate(acc, masks, g.hflip, self.mask_heur, first=i == 0)
+            if views is not None:
+                views.setdefault(v, {}).update(mask_rois=mrois, masks=masks)
+        ops.mask_aug_finish(acc, len(self.mask_views), self.mask_heur)
+        return acc, first[0], first[1], first[2]
+
+    def complete(self, out: dict) -> dict:
+        """FramePipeline.complete; the rare rows past the padded mask batch run through
+        every mask view again."""
+        if "counts_host" in out:
+            return out
+        counts = out["counts"].cpu().tolist()
+        if any(c < 0 for c in counts):
+            bad = [i for i, c in enumerate(counts) if c < 0]
+            raise ops._lib.VosdetError(
+                "test-time augmentation failed for frame(s) %s (count -1): a class's union of "
+                "the box views holds more than cand_cap = %d candidates, or a view's proposal "
+                "selection failed" % (bad, self.cand_cap))
+        if max(counts, default=0) > self.det_cap:
+            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
+        M, cap = sum(counts), out["masks"].shape[0]
+        if M > cap:
+            extra = -(-(M - cap) // 64) * 64
+            m2, r2, f2, _ = self._aug_masks(out, extra, cap)
+            out["masks"] = torch.cat([out["masks"], m2])
+            out["mask_feat"] = torch.cat([out["mask_feat"], f2])
+            out["mask_rois"] = torch.cat([out["mask_rois"], r2])
+        out.pop("_pyrs", None)
+        for k in ("masks", "mask_feat", "mask_rois"):
+            out[k] = out[k][:M]
+        for v in out.get("views", {}).values():
+            for k in ("mask_rois", "masks"):
+                if k in v:
+                    v[k] = v[k][:M]
+        out["counts_host"] = counts
+        return out
 
 
 class RaggedBatch:

@@ -1449,6 +1449,120 @@ def box_detections(rois, cls_prob, bbox_pred, roi_count, im_scale, im_hw, score_
     return dets, cls, cnt
 
 
+UNION_MAX_CAND = 16384  # csrc/box_union.hip kUnionCandMax
+
+
+class BoxUnion:
+    """im_detect_bbox_aug with the UNION heuristics followed by
+    box_results_with_nms_and_limit (lib/core/test.py:193-311, 733-797) on the device:
+    add_view() once per box view in np.vstack order (config.aug_views' box order, the
+    identity view last), then detections().  The per-class candidate lists live in one
+    workspace of vd_box_union_workspace_size(cand_cap, F, K) bytes, allocated here once
+    (no allocation per step)."""
+
+    def __init__(self, cand_cap: int, num_images: int, num_classes: int, device="cuda"):
+        if not 1 <= int(cand_cap) <= UNION_MAX_CAND:
+            raise ValueError("BoxUnion: cand_cap = %r outside [1, %d]" % (cand_cap, UNION_MAX_CAND))
+        self.cand_cap, self.F, self.K = int(cand_cap), int(num_images), int(num_classes)
+        self.ws = _ws(lib().vd_box_union_workspace_size(self.cand_cap, self.F, self.K), device)
+        self.views = 0
+
+    def add_view(self, rois, cls_prob, bbox_pred, roi_count, im_scale, im_hw, hflip: bool,
+                 score_thresh=0.05, bbox_reg_weights=(10., 10., 5., 5.), first=None):
+        """One view's rois [F,R,5], cls_prob [F,R,K], bbox_pred [F,R,4K], roi_count [F],
+        its im_scale [F] fp32 and the ORIGINAL frames' im_hw [F,2] int32.  first (default:
+        the first call after construction or detections()) empties the lists."""
+        r = _need(rois, "rois")
+        p = _need(cls_prob, "cls_prob")
+        d = _need(bbox_pred, "bbox_pred")
+        c = _need(roi_count, "roi_count", torch.int32)
+        s = _need(im_scale, "im_scale")
+        hw = _need(im_hw, "im_hw", torch.int32)
+        N, R, K = p.shape
+        if (N, K) != (self.F, self.K) or tuple(d.shape) != (N, R, 4 * K) or \
+                tuple(r.shape) != (N, R, 5) or c.numel() != N or s.numel() != N or \
+                hw.numel() != 2 * N:
+            raise ValueError("BoxUnion.add_view: rois %s cls_prob %s bbox_pred %s for F = %d, "
+                             "K = %d" % (tuple(r.shape), tuple(p.shape), tuple(d.shape), self.F,
+                                         self.K))
+        first = self.views == 0 if first is None else bool(first)
+        w = (ctypes.c_float * 4)(*[float(np.float32(x)) for x in bbox_reg_weights])
+        check(lib().vd_box_union_add_view(
+            r.data_ptr(), p.data_ptr(), d.data_ptr(), c.data_ptr(), R, N, K, s.data_ptr(),
+            hw.data_ptr(), int(bool(hflip)), int(first), float(np.float32(score_thresh)),
+            ctypes.cast(w, ctypes.c_void_p), self.cand_cap, self.ws.data_ptr(), self.ws.numel(),
+            _stream()), "vd_box_union_add_view")
+        self.views = 1 if first else self.views + 1
+
+    def detections(self, nms_thresh=0.5, dets_per_im=100, det_cap=256, out=None,
+                   nms_cross_class=0., num_det_per_class_pre=0, soft_nms=None,
+                   soft_nms_sigma=0.5, bbox_vote=None, bbox_vote_thresh=0.8, bbox_vote_beta=1.0,
+                   cand_counts=None):
+        """-> (dets [F,cap,5], cls int32 [F,cap], counts int32 [F]) as box_detections
+        returns them; a failed image (a list past cand_cap, a failed view) has count -1.
+        cand_counts: optional int32 [F,K] tensor that receives the lists' lengths."""
+        dev = self.ws.device
+        if out is None:
+            dets = torch.zeros((self.F, det_cap, 5), dtype=torch.float32, device=dev)
+            cls = torch.zeros((self.F, det_cap), dtype=torch.int32, device=dev)
+            cnt = torch.zeros((self.F,), dtype=torch.int32, device=dev)
+        else:
+            dets, cls, cnt = out
+        sm = -1 if soft_nms is None else SOFT_NMS_METHODS[soft_nms]
+        vm = -1 if bbox_vote is None else bbox_vote_method(bbox_vote, bbox_vote_beta)
+        cc = None
+        if cand_counts is not None:
+            cc = _need(cand_counts, "cand_counts", torch.int32)
+            if cc.numel() != self.F * self.K or cc.data_ptr() != cand_counts.data_ptr():
+                raise ValueError("cand_counts must be a contiguous int32 [F, K] tensor")
+        check(lib().vd_box_union_detections(
+            self.cand_cap, self.F, self.K, float(np.float32(nms_thresh)), int(dets_per_im), sm,
+            float(np.float32(soft_nms_sigma)), float(np.float32(0.0001)), vm,
+            float(np.float32(bbox_vote_thresh)), float(bbox_vote_beta), det_cap, dets.data_ptr(),
+            cls.data_ptr(), cnt.data_ptr(), None if cc is None else cc.data_ptr(),
+            self.ws.data_ptr(), self.ws.numel(), _stream()), "vd_box_union_detections")
+        if nms_cross_class > 0 or num_det_per_class_pre > 0:  # the fork's vos_test.py:805-833
+            check(lib().vd_detections_postfilter(dets.data_ptr(), cls.data_ptr(), cnt.data_ptr(),
+                                                 self.F, det_cap,
+                                                 float(np.float32(nms_cross_class)),
+                                                 int(num_det_per_class_pre), _stream()),
+                  "vd_detections_postfilter")
+        self.views = 0
+        return dets, cls, cnt
+
+
+MASK_AUG_HEURS = {"SOFT_AVG": 0, "SOFT_MAX": 1, "LOGIT_AVG": 2}  # include/vosdet.h VD_MASK_AUG_*
+
+
+def mask_aug_accumulate(acc: torch.Tensor, masks: torch.Tensor, hflip: bool, heur: str,
+                        first: bool) -> torch.Tensor:
+    """One view of im_detect_mask_aug's masks_ts (lib/core/test.py:405-476) folded into
+    acc in place (vd_mask_aug_accumulate): masks [M,R,R] class-selected sigmoid outputs,
+    a flipped view read with its last axis reversed; first: the identity view."""
+    a, m = _need(acc, "acc"), _need(masks, "masks")
+    if a.data_ptr() != acc.data_ptr() or a.shape != m.shape or m.dim() != 3 or \
+            m.shape[1] != m.shape[2]:
+        raise ValueError("mask_aug_accumulate: acc %s (contiguous) and masks %s must both be "
+                         "[M, R, R]" % (tuple(acc.shape), tuple(masks.shape)))
+    M, R = m.shape[0], m.shape[2]
+    check(lib().vd_mask_aug_accumulate(a.data_ptr() if M else None, m.data_ptr() if M else None,
+                                       M, R, int(bool(hflip)), MASK_AUG_HEURS[heur],
+                                       int(bool(first)), _stream()), "vd_mask_aug_accumulate")
+    return acc
+
+
+def mask_aug_finish(acc: torch.Tensor, num_views: int, heur: str) -> torch.Tensor:
+    """np.mean / the logistic of the mean logit over the num_views accumulated views, in
+    place (vd_mask_aug_finish); SOFT_MAX needs nothing."""
+    a = _need(acc, "acc")
+    if a.data_ptr() != acc.data_ptr() or a.dim() != 3:
+        raise ValueError("mask_aug_finish: acc must be a contiguous [M, R, R] tensor")
+    M, R = a.shape[0], a.shape[2]
+    check(lib().vd_mask_aug_finish(a.data_ptr() if M else None, M, R, int(num_views),
+                                   MASK_AUG_HEURS[heur], _stream()), "vd_mask_aug_finish")
+    return acc
+
+
 def detections_prev_box_filter(dets: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor,
                                prev_dets: torch.Tensor, prev_classes: torch.Tensor,
                                prev_counts: torch.Tensor, iou_thresh: float,
