@@ -1041,6 +1041,8 @@ def conv3x3_wino4_dilated2_bias_act(x: torch.Tensor, u: torch.Tensor,
     u_ = _need(u, "u")
     if u_.dim() != 6 or tuple(u_.shape[1:]) != (C // 8, 4, 18, 64, 4) or C % 8 or H % 2 or W % 2:
         return None
+    if lay == 1 and (H > 30 or W > 30):  # pairs / octets hold sub-maps of at most 15 x 15
+        return None
     Cout = u_.shape[0] * 64
     b, out = _conv3x3_bias_out(x, bias, Cout, out)
     return _conv3x3_done(lib().vd_conv3x3_wino4_dilated2_bias_act(
