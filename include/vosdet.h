@@ -869,6 +869,41 @@ int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float
                              int box_stride, int min_size, float *out, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * im_detect_keypoints_aug's combination of the views' heatmaps (lib/core/test.py:
+ * 567-651, combine_heatmaps_size_dep :705-730, flip_heatmaps lib/utils/keypoints.py:
+ * 90-100) fused into the decode above: one launch, the combined map is made while a
+ * workgroup loads its (RoI, keypoint) map and everything after is
+ * vd_heatmaps_to_keypoints' code.
+ *
+ * view_maps: HOST array of V device pointers (1 <= V <= 32), each R x K x M x M fp32
+ * logits as the network returned them for that view, in heatmaps_ts order (the
+ * identity view first).  Bit v of hflip_mask: view v saw the flipped image, so it is
+ * read as flip_heatmaps inverts it -- channel flip_perm[k] (HOST, K entries in [0, K):
+ * the left/right swap), column M - 1 - x.  Bits of ds_mask / us_mask: the view's scale
+ * is below / above TEST.SCALE; they are disjoint and bit 0 is clear in both (the
+ * identity view is never dropped).  heur: VD_KPS_AUG_HM_AVG (np.mean over the views:
+ * the float32 sum in view order divided by float(T)) or VD_KPS_AUG_HM_MAX (the running
+ * maximum; NaN logits are unsupported).  area_th < 0: every view counts for every row.
+ * area_th >= 0 (KPS_AUG.SCALE_SIZE_DEP with KPS_AUG.AREA_TH): per row
+ * area = (x2 - x1 + 1) * (y2 - y1 + 1) in float32, each operation rounded; area <
+ * area_th drops the ds views, area >= area_th the us views, and T is the number of
+ * views left for that row.  boxes, box_stride, min_size, out: as above (the unflipped
+ * detection boxes).  combined_out: NULL, or R x K x M x M receiving the combined maps
+ * (each written by exactly one workgroup).  The pointers, masks and permutation are
+ * copied into the kernel's arguments, so a captured graph replays the launch.
+ * Returns VD_ERR_ARG (nothing launched, out untouched) for V outside 1..32, a mask
+ * bit at or above V, ds / us bit 0 set, ds & us != 0, a permutation entry outside
+ * [0, K), an unknown heur, a NaN area_th or a NULL view.  R == 0 launches nothing. */
+#define VD_KPS_AUG_HM_AVG 0
+#define VD_KPS_AUG_HM_MAX 1
+#define VD_KPS_AUG_MAX_VIEWS 32
+int vd_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,
+                                 uint32_t ds_mask, uint32_t us_mask, const int32_t *flip_perm,
+                                 int heur, float area_th, int R, int K, int M,
+                                 const float *boxes, int box_stride, int min_size,
+                                 float *combined_out, float *out, void *stream);
+
+/* ---------------------------------------------------------------------------
  * keypoint_results' OKS NMS (lib/utils/keypoints.py:225-266 nms_oks /
  * compute_oks, applied per frame at lib/core/test.py:864-870 as a Python loop over
  * numpy arrays on the host) on the device, for all F frames of a step in two

@@ -152,6 +152,10 @@ SIGNATURES = {
     "vd_rle_strings": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     # keypoint_results (heatmap decode)
     "vd_heatmaps_to_keypoints": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
+    # im_detect_keypoints_aug's combination fused into the decode
+    "vd_heatmaps_to_keypoints_aug": (_I, [_P, _I, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_uint32, _P, _I, _F, _I, _I, _I, _P, _I, _I,
+                                          _P, _P, _P]),
     # keypoint_results (OKS NMS)
     "vd_nms_oks_frames": (_I, [_P, _L, _I, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P,
                                _P, _P, _P]),

@@ -92,9 +92,13 @@ def default_cfg() -> AttrDict:
             MASK_AUG=_d(ENABLED=False, HEUR="SOFT_AVG", H_FLIP=False, SCALES=(), MAX_SIZE=4000,
                         SCALE_H_FLIP=False, SCALE_SIZE_DEP=False, ASPECT_RATIOS=(),
                         ASPECT_RATIO_H_FLIP=False),
-            # inference options read only to be rejected when enabled (UNSUPPORTED)
+            # config.py:322-351: keypoint test-time augmentation, accepted by
+            # load_cfg(test_aug=True) on a MODEL.KEYPOINTS_ON config only
+            # (engine.KeypointAugFramePipeline); kps_aug_views() lists the views
+            KPS_AUG=_d(ENABLED=False, HEUR="HM_AVG", H_FLIP=False, SCALES=(), MAX_SIZE=4000,
+                       SCALE_H_FLIP=False, SCALE_SIZE_DEP=False, AREA_TH=180 ** 2,
+                       ASPECT_RATIOS=(), ASPECT_RATIO_H_FLIP=False),
             # (NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU below are built: VOSPipeline)
-            KPS_AUG=_d(ENABLED=False),  # config.py:322-351
             NMS_WITH_MASK_IOU=0., NMS_SMALL_BOX_IOU=0.,  # config.py:951-953: the VOS
             NMS_SMALL_BOX_SCORE_THRESHOLD=0.),  # loop's heuristics (engine.VOSPipeline)
         PIXEL_MEANS=(102.9801, 115.9465, 122.7717),  # config.py:1015
@@ -162,7 +166,9 @@ UNSUPPORTED = (
      "a config key: load_cfg(..., test_aug=True) accepts it for engine.AugFramePipeline"),
     ("TEST.MASK_AUG.ENABLED", bool, "mask test-time augmentation, lib/core/test.py:405-526, as "
      "a config key: load_cfg(..., test_aug=True) accepts it for engine.AugFramePipeline"),
-    ("TEST.KPS_AUG.ENABLED", bool, "keypoint test-time augmentation (keypoint heads out of scope)"),
+    ("TEST.KPS_AUG.ENABLED", bool, "keypoint test-time augmentation, lib/core/test.py:567-730, "
+     "as a config key: load_cfg(..., test_aug=True) accepts it on a MODEL.KEYPOINTS_ON config "
+     "for engine.KeypointAugFramePipeline"),
     ("MODEL.USE_DELTA_FLOW", _WithCfg(lambda v, c: bool(v) and not c.get("VOS", False)),
      "delta-flow head on a model other than Generalized_VOS_RCNN: only the VOS builder has it, "
      "lib_vos/vos_modeling/vos_model_builder.py:95-104"),
@@ -188,7 +194,9 @@ def _get(cfg, key):
 
 
 TEST_AUG_KEYS = ("TEST.BBOX_AUG.ENABLED", "TEST.MASK_AUG.ENABLED")
+KPS_AUG_KEY = "TEST.KPS_AUG.ENABLED"  # test_aug accepts it too, on keypoint configs
 MASK_AUG_HEURS = ("SOFT_AVG", "SOFT_MAX", "LOGIT_AVG")
+KPS_AUG_HEURS = ("HM_AVG", "HM_MAX")
 
 
 def _aug_on(aug):
@@ -199,7 +207,19 @@ def _aug_not(aug, allowed):
     return lambda v, c: bool(c.TEST[aug].ENABLED) and v not in allowed
 
 
-# What load_cfg(test_aug=True) still refuses of an enabled TEST.BBOX_AUG / MASK_AUG.
+def _float32_exact(v):
+    """v is a non-negative number that float32 holds exactly (the size-dependent
+    combination compares float32 box areas with it on the device)."""
+    import struct
+    try:
+        f = float(v)
+        return f >= 0 and f == v and struct.unpack("f", struct.pack("f", f))[0] == f
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+# What load_cfg(test_aug=True) still refuses of an enabled TEST.BBOX_AUG / MASK_AUG /
+# KPS_AUG.
 UNSUPPORTED_TEST_AUG = tuple(
     (key, _WithCfg(pred), where) for key, pred, where in (
         ("TEST.BBOX_AUG.ASPECT_RATIOS", _aug_on("BBOX_AUG"),
@@ -216,16 +236,30 @@ UNSUPPORTED_TEST_AUG = tuple(
          "UNION whenever the score heuristic is, lib/core/test.py:199-201"),
         ("TEST.MASK_AUG.HEUR", _aug_not("MASK_AUG", MASK_AUG_HEURS),
          "the reference raises, lib/core/test.py:471-474"),
+        ("TEST.KPS_AUG.ENABLED", lambda v, c: bool(v) and not c.MODEL.KEYPOINTS_ON,
+         "keypoint test-time augmentation needs a MODEL.KEYPOINTS_ON config"),
+        ("TEST.MASK_AUG.ENABLED", lambda v, c: bool(v) and bool(c.MODEL.KEYPOINTS_ON),
+         "a MODEL.KEYPOINTS_ON model has no mask head"),
+        ("TEST.KPS_AUG.ASPECT_RATIOS", _aug_on("KPS_AUG"),
+         "aspect-ratio views need an anisotropic resize, lib/core/test.py:684-702"),
+        ("TEST.KPS_AUG.HEUR", _aug_not("KPS_AUG", KPS_AUG_HEURS),
+         "the reference raises, lib/core/test.py:631-638"),
+        ("TEST.KPS_AUG.AREA_TH", lambda v, c: bool(c.TEST.KPS_AUG.ENABLED) and bool(
+            c.TEST.KPS_AUG.SCALE_SIZE_DEP) and not _float32_exact(v),
+         "with SCALE_SIZE_DEP the threshold must be a non-negative number that float32 holds "
+         "exactly: the float32 box areas are compared with it on the device"),
     ))
 
 
 def check_supported(cfg, test_aug: bool = False) -> None:
     """Raise NotImplementedError naming every enabled option of ``UNSUPPORTED``;
-    test_aug accepts TEST.BBOX_AUG / TEST.MASK_AUG but for ``UNSUPPORTED_TEST_AUG``."""
+    test_aug accepts TEST.BBOX_AUG / TEST.MASK_AUG / TEST.KPS_AUG but for
+    ``UNSUPPORTED_TEST_AUG``."""
     bad = []
     table = UNSUPPORTED
     if test_aug:
-        table = tuple(r for r in UNSUPPORTED if r[0] not in TEST_AUG_KEYS) + UNSUPPORTED_TEST_AUG
+        table = tuple(r for r in UNSUPPORTED if r[0] not in TEST_AUG_KEYS + (KPS_AUG_KEY,)) \
+            + UNSUPPORTED_TEST_AUG
     for key, enabled, where in table:
         try:
             v = _get(cfg, key)
@@ -263,12 +297,40 @@ def aug_views(cfg):
     return box, mask
 
 
+def kps_aug_views(cfg):
+    """The views of im_detect_keypoints_aug in heatmaps_ts order (lib/core/test.py:
+    591-615) -> (views, ds_tags, us_tags): views as aug_views' (scale, max_size, hflip),
+    the identity view FIRST, the flipped view at (TEST.SCALE, TEST.MAX_SIZE), then per
+    KPS_AUG.SCALES entry the view at (scale, KPS_AUG.MAX_SIZE) and its flip with
+    SCALE_H_FLIP.  A scale view is tagged ds when scale < TEST.SCALE and us when
+    scale > TEST.SCALE (combine_heatmaps_size_dep drops ds views for small boxes and us
+    views for large ones); the identity and plain-flip views carry neither.  With
+    KPS_AUG off: the identity view alone."""
+    tst = cfg.TEST
+    aug = tst.KPS_AUG
+    views, ds, us = [(tst.SCALE, tst.MAX_SIZE, False)], [False], [False]
+    if not aug.ENABLED:
+        return views, ds, us
+    if aug.H_FLIP:
+        views.append((tst.SCALE, tst.MAX_SIZE, True))
+        ds.append(False)
+        us.append(False)
+    for s in aug.SCALES:
+        for hf in (False, True) if aug.SCALE_H_FLIP else (False,):
+            views.append((s, aug.MAX_SIZE, hf))
+            ds.append(s < tst.SCALE)
+            us.append(s > tst.SCALE)
+    return views, ds, us
+
+
 def load_cfg(path: str | None = None, overrides: dict | None = None,
              test_aug: bool = False) -> AttrDict:
     """Defaults, then a reference YAML (safe loader), then dotted overrides.
     Raises NotImplementedError if the result enables an ``UNSUPPORTED`` option.
     test_aug=True accepts TEST.BBOX_AUG.ENABLED / TEST.MASK_AUG.ENABLED (the config
-    runs on engine.AugFramePipeline only) and refuses ``UNSUPPORTED_TEST_AUG``."""
+    runs on engine.AugFramePipeline only) and, on a MODEL.KEYPOINTS_ON config,
+    TEST.BBOX_AUG.ENABLED / TEST.KPS_AUG.ENABLED (engine.KeypointAugFramePipeline
+    only); it refuses ``UNSUPPORTED_TEST_AUG``."""
     cfg = default_cfg()
     if path:
         with open(path) as f:

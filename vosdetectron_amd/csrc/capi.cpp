@@ -747,6 +747,32 @@ int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float
                                         VD_STREAM(stream));
 }
 
+int vd_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,
+                                 uint32_t ds_mask, uint32_t us_mask, const int32_t *flip_perm,
+                                 int heur, float area_th, int R, int K, int M,
+                                 const float *boxes, int box_stride, int min_size,
+                                 float *combined_out, float *out, void *stream) {
+    // the arguments are judged before R == 0 returns: an empty step with a bad view
+    // list is still a caller's mistake
+    if (V < 1 || V > VD_KPS_AUG_MAX_VIEWS || K < 1 || K > 32 || M < 1 || M > 64 || R < 0 ||
+        box_stride < 4 || min_size < 0 || !view_maps || !flip_perm)
+        return VD_ERR_ARG;
+    const uint32_t all = V == 32 ? 0xffffffffu : (1u << V) - 1u;
+    if ((hflip_mask | ds_mask | us_mask) & ~all) return VD_ERR_ARG;
+    if (((ds_mask | us_mask) & 1u) || (ds_mask & us_mask)) return VD_ERR_ARG;
+    if (heur != VD_KPS_AUG_HM_AVG && heur != VD_KPS_AUG_HM_MAX) return VD_ERR_ARG;
+    if (area_th != area_th) return VD_ERR_ARG;
+    for (int k = 0; k < K; ++k)
+        if (flip_perm[k] < 0 || flip_perm[k] >= K) return VD_ERR_ARG;
+    if (R == 0) return VD_OK;
+    if (!boxes || !out) return VD_ERR_ARG;
+    for (int v = 0; v < V; ++v)
+        if (!view_maps[v]) return VD_ERR_ARG;
+    return launch_heatmaps_to_keypoints_aug(view_maps, V, hflip_mask, ds_mask, us_mask, flip_perm,
+                                            heur, area_th, R, K, M, boxes, box_stride, min_size,
+                                            combined_out, out, VD_STREAM(stream));
+}
+
 int vd_nms_oks_frames(const float *keyps, int64_t keyps_rows, int K, const float *dets,
                       const int32_t *classes, const int32_t *counts, int F, int D, double thresh,
                       int32_t *keep, int32_t *counts_out, float *dets_out, int32_t *classes_out,

@@ -35,6 +35,11 @@
 //   c2 = ((A+2)*(1-t) - (A+3))*(1-t)*(1-t) + 1
 //   c3 = 1 - c0 - c1 - c2
 //   value = ((S0*c0 + S1*c1) + S2*c2) + S3*c3, rows first, then columns.
+//
+// The kernel is a template on what fills src: KpPlainMaps copies the map
+// (vd_heatmaps_to_keypoints), KpAugMaps makes it from the TEST.KPS_AUG views
+// (vd_heatmaps_to_keypoints_aug: im_detect_keypoints_aug's combination, lib/core/test.py:
+// 567-730).  Everything after the fill is shared.
 #include "common.hpp"
 #include "vosdet_internal.hpp"
 
@@ -80,8 +85,70 @@ __device__ __forceinline__ bool kp_better(float v, int i, float bv, int bi) {
     return v > bv || (v == bv && i < bi);
 }
 
+// The map a workgroup decodes: one R x K x M x M array read as it is.
+struct KpPlainMaps {
+    const float *maps;
+    __device__ __forceinline__ void fill(float *src, int r, int k, int K, int M,
+                                         const float *b) const {
+        const float *m = maps + ((int64_t)r * K + k) * M * M;
+        for (int i = threadIdx.x; i < M * M; i += blockDim.x) src[i] = m[i];
+    }
+};
+
+// The map a workgroup decodes: im_detect_keypoints_aug's combination of V views
+// (lib/core/test.py:567-651, 705-730), made while the map is loaded.  Per element the
+// views are walked in heatmaps_ts order: a view the row's box area drops is skipped
+// (combine_heatmaps_size_dep: area < area_th drops the ds views, area >= area_th the us
+// views; area = (x2 - x1 + 1) * (y2 - y1 + 1) in float32, every operation rounded), a
+// flipped view is read as flip_heatmaps inverts it (channel perm[k], column M - 1 - x),
+// and the values fold as np.mean / np.amax over axis 0 do: the first kept value, then
+// + or max in order, HM_AVG divided by float(T_row) (the float64 quotient of float32
+// operands rounded to float32 is the correctly rounded float32 quotient).  Everything
+// travels by value in the kernel arguments: no device-side pointer table.
+struct KpAugMaps {
+    const float *maps[VD_KPS_AUG_MAX_VIEWS];
+    int8_t perm[kKpMaxK];
+    uint32_t hflip, ds, us;
+    int V, heur;
+    float area_th;
+    float *combined;  // R x K x M x M or nullptr
+    __device__ __forceinline__ void fill(float *src, int r, int k, int K, int M,
+                                         const float *b) const {
+        uint32_t keep = V >= 32 ? 0xffffffffu : (1u << V) - 1u;
+        if (area_th >= 0.f) {
+            const float bw = b[2] - b[0] + 1.f, bh = b[3] - b[1] + 1.f;
+            const float area = bw * bh;
+            keep &= area < area_th ? ~ds : ~us;
+        }
+        const float T = (float)__popc(keep);
+        const int64_t plain = ((int64_t)r * K + k) * M * M;
+        const int64_t swapped = ((int64_t)r * K + perm[k]) * M * M;
+        float *c = combined ? combined + plain : nullptr;
+        for (int i = threadIdx.x; i < M * M; i += blockDim.x) {
+            const int y = i / M, x = i - y * M;
+            const int fi = y * M + (M - 1 - x);
+            float acc = 0.f;
+            bool any = false;
+            for (int v = 0; v < V; ++v) {
+                if (!((keep >> v) & 1u)) continue;
+                const bool hf = (hflip >> v) & 1u;
+                const float val = hf ? maps[v][swapped + fi] : maps[v][plain + i];
+                if (!any)
+                    acc = val;
+                else
+                    acc = heur == VD_KPS_AUG_HM_MAX ? fmaxf(acc, val) : acc + val;
+                any = true;
+            }
+            if (heur == VD_KPS_AUG_HM_AVG) acc = (float)((double)acc / (double)T);
+            src[i] = acc;
+            if (c) c[i] = acc;
+        }
+    }
+};
+
+template <class Maps>
 __global__ __launch_bounds__(kKpWaves * VD_WAVE) void heatmaps_to_keypoints_kernel(
-    const float *__restrict__ maps, int K, int M, const float *__restrict__ boxes,
+    const Maps maps, int K, int M, const float *__restrict__ boxes,
     int box_stride, int min_size, float *__restrict__ out) {
     __shared__ float src[kKpMaxM * kKpMaxM];
     __shared__ float hz[kKpMaxM * kKpStrip];
@@ -90,10 +157,9 @@ __global__ __launch_bounds__(kKpWaves * VD_WAVE) void heatmaps_to_keypoints_kern
     __shared__ double red_s[kKpWaves];
     const int r = blockIdx.x / K, k = blockIdx.x - r * K;
     const int lane = lane_id(), wv = wave_id();
-    const float *m = maps + (int64_t)blockIdx.x * M * M;
-    for (int i = threadIdx.x; i < M * M; i += blockDim.x) src[i] = m[i];
-
     const float *b = boxes + (int64_t)r * box_stride;
+    maps.fill(src, r, k, K, M, b);
+
     const float x1 = b[0], y1 = b[1];
     const float w = fmaxf(b[2] - x1, 1.f), h = fmaxf(b[3] - y1, 1.f);
     int Wm = (int)ceilf(w), Hm = (int)ceilf(h);
@@ -197,8 +263,33 @@ int launch_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const f
     if (R == 0) return VD_OK;
     if (M < 1 || M > kKpMaxM || K < 1 || K > kKpMaxK) return VD_ERR_SHAPE;
     if ((int64_t)R * K > 0x7fffffffll) return VD_ERR_SHAPE;
-    hipLaunchKernelGGL(heatmaps_to_keypoints_kernel, dim3(R * K), dim3(kKpWaves * VD_WAVE), 0, s,
-                       maps, K, M, boxes, box_stride, min_size, out);
+    hipLaunchKernelGGL(heatmaps_to_keypoints_kernel<KpPlainMaps>, dim3(R * K),
+                       dim3(kKpWaves * VD_WAVE), 0, s, KpPlainMaps{maps}, K, M, boxes, box_stride,
+                       min_size, out);
+    return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
+}
+
+int launch_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,
+                                     uint32_t ds_mask, uint32_t us_mask, const int32_t *flip_perm,
+                                     int heur, float area_th, int R, int K, int M,
+                                     const float *boxes, int box_stride, int min_size,
+                                     float *combined_out, float *out, hipStream_t s) {
+    if (R == 0) return VD_OK;
+    if (M < 1 || M > kKpMaxM || K < 1 || K > kKpMaxK) return VD_ERR_SHAPE;
+    if (V < 1 || V > VD_KPS_AUG_MAX_VIEWS) return VD_ERR_SHAPE;
+    if ((int64_t)R * K > 0x7fffffffll) return VD_ERR_SHAPE;
+    KpAugMaps a = {};
+    for (int v = 0; v < V; ++v) a.maps[v] = view_maps[v];
+    for (int k = 0; k < K; ++k) a.perm[k] = (int8_t)flip_perm[k];
+    a.hflip = hflip_mask;
+    a.ds = ds_mask;
+    a.us = us_mask;
+    a.V = V;
+    a.heur = heur;
+    a.area_th = area_th;
+    a.combined = combined_out;
+    hipLaunchKernelGGL(heatmaps_to_keypoints_kernel<KpAugMaps>, dim3(R * K),
+                       dim3(kKpWaves * VD_WAVE), 0, s, a, K, M, boxes, box_stride, min_size, out);
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 

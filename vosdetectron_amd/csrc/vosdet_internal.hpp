@@ -233,6 +233,11 @@ int launch_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, in
 
 int launch_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                                  int box_stride, int min_size, float *out, hipStream_t s);
+int launch_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,
+                                     uint32_t ds_mask, uint32_t us_mask, const int32_t *flip_perm,
+                                     int heur, float area_th, int R, int K, int M,
+                                     const float *boxes, int box_stride, int min_size,
+                                     float *combined_out, float *out, hipStream_t s);
 
 // keypoint_results' OKS NMS (oks_nms.hip)
 int launch_nms_oks_frames(const float *keyps, int64_t rows, int K, const float *dets,

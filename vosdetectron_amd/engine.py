@@ -24,6 +24,9 @@ KeypointFramePipeline runs the Keypoint R-CNN configs: after misc_bbox, the pose
 and vd_heatmaps_to_keypoints (im_detect_keypoints + keypoint_results, test.py:97-107)
 take the mask stage's place; frame_keypoints groups the result as cls_keyps.
 KeypointFramePipeline(nms_oks=...) adds keypoint_results' OKS NMS (vd_nms_oks_frames).
+KeypointAugFramePipeline runs the keypoint configs with TEST.BBOX_AUG / TEST.KPS_AUG
+(im_detect_keypoints_aug, test.py:567-730): vd_heatmaps_to_keypoints_aug combines the
+views' heatmaps inside the decode.
 """
 from __future__ import annotations
 
@@ -96,12 +99,23 @@ class FramePipeline:
                 "%s: MODEL.KEYPOINTS_ON configs run on KeypointFramePipeline (FPN, frames of "
                 "one size); ragged, C4 and VOS keypoint steps are not built"
                 % type(self).__name__)
+        if (cfg.TEST.BBOX_AUG.ENABLED or cfg.TEST.KPS_AUG.ENABLED) \
+                and isinstance(self, KeypointFramePipeline) \
+                and not isinstance(self, KeypointAugFramePipeline):
+            raise NotImplementedError(
+                "%s: TEST.BBOX_AUG / TEST.KPS_AUG on a keypoint config run on "
+                "KeypointAugFramePipeline (FPN, frames of one size)" % type(self).__name__)
         if (cfg.TEST.BBOX_AUG.ENABLED or cfg.TEST.MASK_AUG.ENABLED) \
-                and not isinstance(self, AugFramePipeline):
+                and not isinstance(self, (AugFramePipeline, KeypointAugFramePipeline)):
             raise NotImplementedError(
                 "%s: TEST.BBOX_AUG / TEST.MASK_AUG run on AugFramePipeline (FPN mask configs, "
-                "frames of one size); ragged, C4, VOS and keypoint steps with test-time "
-                "augmentation are not built" % type(self).__name__)
+                "frames of one size) and, for keypoint configs, on KeypointAugFramePipeline; "
+                "ragged, C4 and VOS steps with test-time augmentation are not built"
+                % type(self).__name__)
+        if cfg.TEST.KPS_AUG.ENABLED and not isinstance(self, KeypointAugFramePipeline):
+            raise NotImplementedError(
+                "%s: TEST.KPS_AUG runs on KeypointAugFramePipeline (FPN keypoint configs, "
+                "frames of one size)" % type(self).__name__)
         if not cfg.MODEL.KEYPOINTS_ON and not hasattr(model, "Mask_Head"):
             raise NotImplementedError(
                 "%s: the model has no Mask_Head (MODEL.MASK_ON False); a box-only step is "
@@ -204,6 +218,15 @@ class FramePipeline:
                 self._collect_marks()
 
     def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
+        out, F, pyr, fast, im_scale_d = self._detect(frames, keep_intermediates)
+        self._roi_heads(out, F, pyr, fast, im_scale_d, keep_intermediates)
+        if sync:
+            self.complete(out)
+        return out
+
+    def _detect(self, frames: torch.Tensor, keep_intermediates: bool = False):
+        """im_detect_bbox and box_results_with_nms_and_limit of one step: the body, the
+        box stages and the detections.  -> (out, F, NHWC pyramid, fast, im_scale fp64)."""
         cfg = self.cfg
         F, im_info, im_scale_t, im_scale_d, im_hw = self._frame_rows(frames)
         feats = self.backbone(frames)
@@ -225,10 +248,7 @@ class FramePipeline:
                "cls_prob": cls_prob, "bbox_pred": bbox_pred}
         if keep_intermediates:  # for stage-wise parity tests
             out.update(feats=feats, rpn_probs=probs, rpn_deltas=deltas, pyramid=pyr)
-        self._roi_heads(out, F, pyr, fast, im_scale_d, keep_intermediates)
-        if sync:
-            self.complete(out)
-        return out
+        return out, F, pyr, fast, im_scale_d
 
     def _box_stages(self, feats, im_info):
         """im_detect_bbox's stages between the body and the decode, for the frames
@@ -384,9 +404,9 @@ class KeypointFramePipeline(FramePipeline):
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
         self._ones_d = torch.ones((batch,), dtype=torch.float64, device=self.device)
 
-    def _keypoint_batch(self, pyr, krois, klvl, kboxes, fast):
-        """RoIAlign + head + outputs + decode of a padded batch (padding rows are zero
-        boxes: a 1 x 1 resized map, never read)."""
+    def _keypoint_heatmaps(self, pyr, krois, klvl, fast):
+        """im_detect_keypoints of a padded batch: RoIAlign + head + outputs -> (the
+        [rows,K,S,S] logits, the RoI features as NCHW)."""
         kc = self.cfg.KRCNN
         head = self.model.Keypoint_Head
         if fast and getattr(head, "nhwc_ready", False):
@@ -398,9 +418,14 @@ class KeypointFramePipeline(FramePipeline):
             kfeat = ops.roi_align_fpn(pyr, self.roi_scales, krois, klvl, kc.ROI_XFORM_RESOLUTION,
                                       kc.ROI_XFORM_SAMPLING_RATIO)
             x = head.head(kfeat)
-        heat = self.model.Keypoint_Outs(x).contiguous()
+        return self.model.Keypoint_Outs(x).contiguous(), kfeat
+
+    def _keypoint_batch(self, pyr, krois, klvl, kboxes, fast):
+        """RoIAlign + head + outputs + decode of a padded batch (padding rows are zero
+        boxes: a 1 x 1 resized map, never read)."""
+        heat, kfeat = self._keypoint_heatmaps(pyr, krois, klvl, fast)
         self._mark("im_detect_keypoints")
-        keyps = ops.heatmaps_to_keypoints(heat, kboxes, kc.INFERENCE_MIN_SIZE)
+        keyps = ops.heatmaps_to_keypoints(heat, kboxes, self.cfg.KRCNN.INFERENCE_MIN_SIZE)
         self._mark("misc_keypoints")
         return keyps, heat, kfeat
 
@@ -434,6 +459,10 @@ class KeypointFramePipeline(FramePipeline):
         if keep_intermediates:
             out.update(kps_heatmaps=heat, kps_feat=kfeat, kps_boxes=kboxes)
         out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
+        self._oks_stage(out, keyps, keep_intermediates)
+
+    def _oks_stage(self, out, keyps, keep_intermediates):
+        """With nms_oks: the step's OKS NMS of the detections and their raw keypoints."""
         if self.oks_thresh is not None:
             pre = {k: out[k] for k in ("dets", "classes", "counts", "keyps")}
             out["_oks_pre"] = pre
@@ -441,6 +470,16 @@ class KeypointFramePipeline(FramePipeline):
                 out.update({k + "_pre_oks": v for k, v in pre.items()})
             self._oks_nms(out, pre, keyps)
             self._mark("misc_oks_nms")
+
+    def _raise_on_failed_counts(self, counts):
+        ops.raise_on_failed_counts(counts)
+
+    def _keypoint_overflow(self, out, src, rows, row0):
+        """complete()'s second batch: rows [row0, row0 + rows) of src's detections ->
+        (their keypoints, the kps_* tensors of those rows)."""
+        r2, l2, b2, _ = self._keypoint_rows(src, out["_im_scale_d"], rows, row0=row0)
+        k2, h2, f2 = self._keypoint_batch(out["_pyr"], r2, l2, b2, out["_fast"])
+        return k2, {"kps_rois": r2, "kps_heatmaps": h2, "kps_feat": f2, "kps_boxes": b2}
 
     def complete(self, out: dict) -> dict:
         """FramePipeline.complete for the keypoint outputs: the one host read, the
@@ -459,7 +498,7 @@ class KeypointFramePipeline(FramePipeline):
             F = out["counts"].numel()
             both = torch.cat([pre["counts"], out["counts"]]).cpu().tolist()
             before, counts = both[:F], both[F:]
-        ops.raise_on_failed_counts(before)
+        self._raise_on_failed_counts(before)
         if max(before, default=0) > self.det_cap:
             raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, before))
         keep = out.pop("_kps_keep", False)
@@ -468,9 +507,7 @@ class KeypointFramePipeline(FramePipeline):
         M, cap = sum(before), raw.shape[0]
         if M > cap:  # rows [cap, M): a second, rare batch
             extra = -(-(M - cap) // 64) * 64
-            r2, l2, b2, _ = self._keypoint_rows(pre or out, out["_im_scale_d"], extra, row0=cap)
-            k2, h2, f2 = self._keypoint_batch(out["_pyr"], r2, l2, b2, out["_fast"])
-            more = {"kps_rois": r2, "kps_heatmaps": h2, "kps_feat": f2, "kps_boxes": b2}
+            k2, more = self._keypoint_overflow(out, pre or out, extra, cap)
             for k in keys:
                 out[k] = torch.cat([out[k], more[k]])
             raw = torch.cat([raw, k2])
@@ -478,10 +515,15 @@ class KeypointFramePipeline(FramePipeline):
                 self._oks_nms(out, pre, raw)
                 counts = out["counts"].cpu().tolist()
         out.pop("_pyr", None)
+        out.pop("_pyrs", None)
         out.pop("_fast", None)
         out.pop("_im_scale_d", None)
         for k in keys:
             out[k] = out[k][:M]
+        for v in out.get("views", {}).values():  # KeypointAugFramePipeline's per-view rows
+            for k in ("kps_rois", "kps_heatmaps", "kps_feat"):
+                if k in v:
+                    v[k] = v[k][:M]
         if pre is None:
             out["keyps"] = raw[:M]
         else:
@@ -530,7 +572,114 @@ class _ViewGeom:
         self.im_scale_d = torch.full((F,), self.scale, dtype=torch.float64, device=device)
 
 
-class AugFramePipeline(FramePipeline):
+class _AugViews:
+    """What the test-time-augmentation pipelines share: the views' geometry, their
+    blobs and bodies, and im_detect_bbox_aug's box pass over the box views."""
+
+    def _make_geoms(self, views, batch):
+        self.geom = {}
+        for v in views:
+            if v not in self.geom:
+                self.geom[v] = _ViewGeom(v, self.H, self.W, self.cfg.FPN.COARSEST_STRIDE, batch,
+                                         self.device)
+        self._unions = {}
+
+    def pyramid_bytes(self, g) -> int:
+        """Bytes of one frame's RoI pyramid (P2..P5, FPN.DIM channels, fp32) at view g."""
+        n = 0
+        for lvl in self.roi_levels:
+            n += -(-g.Hp // 2 ** lvl) * -(-g.Wp // 2 ** lvl)
+        return n * int(self.cfg.FPN.DIM) * 4
+
+    def _view_blob(self, frames, g):
+        """make_blob at view g's geometry."""
+        nhwc = self.channels_last
+        if g.scale == 1.0:
+            blob = ops.image_to_blob(frames, self.lut, g.Hp, g.Wp, nhwc=nhwc)
+        else:
+            blob = ops.image_resize_to_blob(frames, self.lut, g.scale, g.Hp, g.Wp, nhwc=nhwc)
+        return blob.permute(0, 3, 1, 2) if nhwc else blob
+
+    def _union(self, F, K):
+        if (F, K) not in self._unions:
+            self._unions[(F, K)] = ops.BoxUnion(self.cand_cap, F, K, self.device)
+        return self._unions[(F, K)]
+
+    def _flipped_frames(self, frames):
+        return frames.flip(2) if any(v[2] for v in self.geom) else None
+
+    def _box_pass(self, frames, flipped, head_views, keep_intermediates):
+        """im_detect_bbox_aug + box_results_with_nms_and_limit: every box view's body and
+        box stages folded into the union, then the detections.  A view of head_views
+        keeps its pyramid for the head pass.  -> (out, pyrs, views)."""
+        cfg, tst = self.cfg, self.cfg.TEST
+        F = frames.shape[0]
+        im_hw = self.im_hw[:F]
+        head_set = set(head_views)
+        pyrs, views, union = {}, {}, None
+        for i, v in enumerate(self.box_views):
+            g = self.geom[v]
+            blob = self._view_blob(flipped if g.hflip else frames, g)
+            feats = self.model.Conv_Body(blob)
+            self._mark("conv_body")
+            rois, rcnt, cls_prob, bbox_pred, _, _, pyr, fast, post = \
+                self._box_stages(feats, g.im_info[:F])
+            K = cls_prob.shape[1]
+            bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
+            union = union or self._union(F, K)
+            union.add_view(rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
+                           g.im_scale_t[:F], im_hw, g.hflip, tst.SCORE_THRESH,
+                           cfg.MODEL.BBOX_REG_WEIGHTS, first=i == 0)
+            self._mark("union_add_view")
+            if v in head_set:
+                pyrs[v] = (pyr, fast)
+            if keep_intermediates:
+                views[v] = dict(rois=rois, roi_counts=rcnt, cls_prob=cls_prob,
+                                bbox_pred=bbox_pred, pyramid=pyr, blob=blob)
+        cand = torch.zeros((F, K), dtype=torch.int32, device=self.device)
+        dets, dcls, dcnt = union.detections(
+            tst.NMS, tst.DETECTIONS_PER_IM, self.det_cap, nms_cross_class=tst.NMS_CROSS_CLASS,
+            num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE, cand_counts=cand,
+            **self._nms_options)
+        self._mark("misc_bbox")
+        ident = views.get(self.box_views[-1]) or dict(rois=rois, roi_counts=rcnt,
+                                                      cls_prob=cls_prob, bbox_pred=bbox_pred)
+        out = {"dets": dets, "classes": dcls, "counts": dcnt, "cand_counts": cand,
+               "rois": ident["rois"], "roi_counts": ident["roi_counts"],
+               "cls_prob": ident["cls_prob"], "bbox_pred": ident["bbox_pred"]}
+        return out, pyrs, views
+
+    def _body_only(self, frames, flipped, head_views, pyrs, views, keep_intermediates):
+        """The bodies of the head views the box pass did not run (the reference's
+        im_conv_body_only), added to pyrs."""
+        for v in head_views:
+            if v not in pyrs:
+                g = self.geom[v]
+                blob = self._view_blob(flipped if g.hflip else frames, g)
+                pyrs[v] = (self.nhwc_pyramid(self.model.Conv_Body(blob)),
+                           self.channels_last and getattr(self.model.Box_Head, "nhwc_ready",
+                                                          False))
+                self._mark("conv_body")
+                if keep_intermediates:
+                    views.setdefault(v, {}).update(pyramid=pyrs[v][0], blob=blob)
+
+    def _hflip_dets(self, dets):
+        """flip_boxes of the detections, float32: x1' = (W - x2) - 1."""
+        dets_hf = dets.clone()
+        dets_hf[..., 0] = self.W - dets[..., 2] - 1
+        dets_hf[..., 2] = self.W - dets[..., 0] - 1
+        return dets_hf
+
+    def _raise_on_failed_union(self, counts):
+        if any(c < 0 for c in counts):
+            bad = [i for i, c in enumerate(counts) if c < 0]
+            raise ops._lib.VosdetError(
+                "test-time augmentation failed for frame(s) %s (count -1): a class's union of "
+                "the box views holds more than cand_cap = %d candidates, or a view's proposal "
+                "selection failed" % (bad, self.cand_cap))
+
+
+class AugFramePipeline(_AugViews, FramePipeline):
     """FramePipeline with the reference's test-time augmentation (TEST.BBOX_AUG /
     TEST.MASK_AUG, lib/core/test.py:193-363, 405-526) for the FPN mask configs and
     frames of one size; cfg comes from config.load_cfg(..., test_aug=True).
@@ -560,15 +709,12 @@ class AugFramePipeline(FramePipeline):
         if not cfg.FPN.FPN_ON or bool(cfg.get("VOS", False)) or cfg.MODEL.KEYPOINTS_ON:
             raise NotImplementedError(
                 "AugFramePipeline: FPN mask configs only (test-time augmentation on the C4, "
-                "VOS and keypoint pipelines is not built)")
+                "VOS and keypoint pipelines is not built; keypoint configs run on "
+                "KeypointAugFramePipeline)")
         vcfg.check_supported(cfg, test_aug=True)
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
         self.box_views, self.mask_views = vcfg.aug_views(cfg)
-        st = cfg.FPN.COARSEST_STRIDE
-        self.geom = {}
-        for v in self.box_views + self.mask_views:
-            if v not in self.geom:
-                self.geom[v] = _ViewGeom(v, self.H, self.W, st, batch, self.device)
+        self._make_geoms(self.box_views + self.mask_views, batch)
         self.mask_heur = cfg.TEST.MASK_AUG.HEUR if cfg.TEST.MASK_AUG.ENABLED else "SOFT_AVG"
         post = int(cfg.TEST.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
         self.cand_cap = int(cand_cap or min(ops.UNION_MAX_CAND, len(self.box_views) * post))
@@ -578,77 +724,12 @@ class AugFramePipeline(FramePipeline):
                 "AugFramePipeline: the %d mask views' pyramids take %d x %d bytes, over "
                 "pyramid_budget_bytes = %d (fewer frames per step, or fewer MASK_AUG views)"
                 % (len(set(self.mask_views)), batch, kept, pyramid_budget_bytes))
-        self._unions = {}
-
-    def pyramid_bytes(self, g) -> int:
-        """Bytes of one frame's RoI pyramid (P2..P5, FPN.DIM channels, fp32) at view g."""
-        n = 0
-        for lvl in self.roi_levels:
-            n += -(-g.Hp // 2 ** lvl) * -(-g.Wp // 2 ** lvl)
-        return n * int(self.cfg.FPN.DIM) * 4
-
-    def _view_blob(self, frames, g):
-        """make_blob at view g's geometry."""
-        nhwc = self.channels_last
-        if g.scale == 1.0:
-            blob = ops.image_to_blob(frames, self.lut, g.Hp, g.Wp, nhwc=nhwc)
-        else:
-            blob = ops.image_resize_to_blob(frames, self.lut, g.scale, g.Hp, g.Wp, nhwc=nhwc)
-        return blob.permute(0, 3, 1, 2) if nhwc else blob
-
-    def _union(self, F, K):
-        if (F, K) not in self._unions:
-            self._unions[(F, K)] = ops.BoxUnion(self.cand_cap, F, K, self.device)
-        return self._unions[(F, K)]
 
     def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
-        cfg, tst = self.cfg, self.cfg.TEST
         F = frames.shape[0]
-        im_hw = self.im_hw[:F]
-        flipped = frames.flip(2) if any(v[2] for v in self.geom) else None
-        mask_set = set(self.mask_views)
-        pyrs, views, union = {}, {}, None
-        for i, v in enumerate(self.box_views):
-            g = self.geom[v]
-            blob = self._view_blob(flipped if g.hflip else frames, g)
-            feats = self.model.Conv_Body(blob)
-            self._mark("conv_body")
-            rois, rcnt, cls_prob, bbox_pred, _, _, pyr, fast, post = \
-                self._box_stages(feats, g.im_info[:F])
-            K = cls_prob.shape[1]
-            bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
-            union = union or self._union(F, K)
-            union.add_view(rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
-                           g.im_scale_t[:F], im_hw, g.hflip, tst.SCORE_THRESH,
-                           cfg.MODEL.BBOX_REG_WEIGHTS, first=i == 0)
-            self._mark("union_add_view")
-            if v in mask_set:
-                pyrs[v] = (pyr, fast)
-            if keep_intermediates:
-                views[v] = dict(rois=rois, roi_counts=rcnt, cls_prob=cls_prob,
-                                bbox_pred=bbox_pred, pyramid=pyr, blob=blob)
-        cand = torch.zeros((F, K), dtype=torch.int32, device=self.device)
-        dets, dcls, dcnt = union.detections(
-            tst.NMS, tst.DETECTIONS_PER_IM, self.det_cap, nms_cross_class=tst.NMS_CROSS_CLASS,
-            num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE, cand_counts=cand,
-            **self._nms_options)
-        self._mark("misc_bbox")
-        ident = views.get(self.box_views[-1]) or dict(rois=rois, roi_counts=rcnt,
-                                                      cls_prob=cls_prob, bbox_pred=bbox_pred)
-        out = {"dets": dets, "classes": dcls, "counts": dcnt, "cand_counts": cand,
-               "rois": ident["rois"], "roi_counts": ident["roi_counts"],
-               "cls_prob": ident["cls_prob"], "bbox_pred": ident["bbox_pred"]}
-        # the mask-only views' bodies (the reference's im_conv_body_only)
-        for v in self.mask_views:
-            if v not in pyrs:
-                g = self.geom[v]
-                blob = self._view_blob(flipped if g.hflip else frames, g)
-                pyrs[v] = (self.nhwc_pyramid(self.model.Conv_Body(blob)),
-                           self.channels_last and getattr(self.model.Box_Head, "nhwc_ready",
-                                                          False))
-                self._mark("conv_body")
-                if keep_intermediates:
-                    views.setdefault(v, {}).update(pyramid=pyrs[v][0], blob=blob)
+        flipped = self._flipped_frames(frames)
+        out, pyrs, views = self._box_pass(frames, flipped, self.mask_views, keep_intermediates)
+        self._body_only(frames, flipped, self.mask_views, pyrs, views, keep_intermediates)
         if keep_intermediates:
             out["views"] = views
         out["_pyrs"] = pyrs
@@ -672,10 +753,8 @@ class AugFramePipeline(FramePipeline):
             g = self.geom[v]
             d = dets
             if g.hflip:
-                if dets_hf is None:  # flip_boxes, float32: x1' = (W - x2) - 1
-                    dets_hf = dets.clone()
-                    dets_hf[..., 0] = self.W - dets[..., 2] - 1
-                    dets_hf[..., 2] = self.W - dets[..., 0] - 1
+                if dets_hf is None:
+                    dets_hf = self._hflip_dets(dets)
                 d = dets_hf
             mrois, mlvl, mcls, mtotal = ops.mask_rois(
                 d, dcls, dcnt, g.im_scale_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
@@ -698,12 +777,7 @@ class AugFramePipeline(FramePipeline):
         if "counts_host" in out:
             return out
         counts = out["counts"].cpu().tolist()
-        if any(c < 0 for c in counts):
-            bad = [i for i, c in enumerate(counts) if c < 0]
-            raise ops._lib.VosdetError(
-                "test-time augmentation failed for frame(s) %s (count -1): a class's union of "
-                "the box views holds more than cand_cap = %d candidates, or a view's proposal "
-                "selection failed" % (bad, self.cand_cap))
+        self._raise_on_failed_union(counts)
         if max(counts, default=0) > self.det_cap:
             raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
         M, cap = sum(counts), out["masks"].shape[0]
@@ -722,6 +796,154 @@ class AugFramePipeline(FramePipeline):
                     v[k] = v[k][:M]
         out["counts_host"] = counts
         return out
+
+
+class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
+    """KeypointFramePipeline with the reference's test-time augmentation (TEST.BBOX_AUG
+    and TEST.KPS_AUG, lib/core/test.py:193-363, 567-730) for the FPN keypoint configs
+    and frames of one size; cfg comes from config.load_cfg(..., test_aug=True).
+
+      box pass: with BBOX_AUG AugFramePipeline's (every box view into the union, then
+      the detections), without it KeypointFramePipeline's single identity view
+      --> per keypoint view (config.kps_aug_views, the identity view first): the
+      detections (flip_boxes for a flipped view) --> vd_mask_rois at the view's scale
+      --> keypoint RoIAlign + Keypoint_Head + Keypoint_Outs on the view's pyramid (kept
+      from the box pass when the view is a box view too, otherwise the body runs as
+      im_conv_body_only does)
+      --> vd_heatmaps_to_keypoints_aug: the views' heatmaps combined (flip_heatmaps of
+      the flipped views, HM_AVG / HM_MAX, with SCALE_SIZE_DEP the views chosen per box
+      by its area against AREA_TH) and decoded against the stored detection boxes in
+      one launch --> the optional OKS NMS (nms_oks).
+
+    All V views' heatmaps are alive at the decode: heatmap_budget_bytes bounds V x the
+    padded batch's rows x K x S x S x 4 bytes, pyramid_budget_bytes batch x the kept
+    pyramids.  The result dict is KeypointFramePipeline's.  keep_intermediates adds
+    out["views"][view] with kps_rois, kps_heatmaps (as the network returned them, not
+    inverted) and kps_feat (and the box views' tensors as AugFramePipeline's),
+    out["kps_heatmaps"] = the combined maps, out["kps_boxes"]; kps_rois / kps_feat are
+    the identity view's.  Stage marks: conv_body, union_add_view, misc_bbox,
+    im_detect_keypoints, misc_keypoints, misc_oks_nms."""
+
+    def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
+                 det_cap=256, device="cuda", nms_oks=None, cand_cap=None,
+                 pyramid_budget_bytes=24 << 30, heatmap_budget_bytes=8 << 30):
+        from . import config as vcfg
+        vcfg.check_supported(cfg, test_aug=True)
+        super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device, nms_oks)
+        tst = cfg.TEST
+        self.bbox_aug = bool(tst.BBOX_AUG.ENABLED)
+        self.box_views = vcfg.aug_views(cfg)[0]
+        self.kps_views, self.kps_ds, self.kps_us = vcfg.kps_aug_views(cfg)
+        if len(set(self.kps_views)) != len(self.kps_views):
+            raise ValueError("KeypointAugFramePipeline: TEST.KPS_AUG lists a view twice: %s"
+                             % (self.kps_views,))
+        if len(self.kps_views) > ops.KPS_AUG_MAX_VIEWS:
+            raise ValueError("KeypointAugFramePipeline: %d keypoint views, the combination "
+                             "takes %d" % (len(self.kps_views), ops.KPS_AUG_MAX_VIEWS))
+        self._make_geoms(self.box_views + self.kps_views, batch)
+        self.kps_heur = tst.KPS_AUG.HEUR if tst.KPS_AUG.ENABLED else "HM_AVG"
+        self.kps_area_th = float(tst.KPS_AUG.AREA_TH) \
+            if tst.KPS_AUG.ENABLED and tst.KPS_AUG.SCALE_SIZE_DEP else None
+        post = int(tst.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
+        self.cand_cap = int(cand_cap or min(ops.UNION_MAX_CAND, len(self.box_views) * post))
+        kept = sum(self.pyramid_bytes(self.geom[v]) for v in self.kps_views)
+        if batch * kept > pyramid_budget_bytes:
+            raise ValueError(
+                "KeypointAugFramePipeline: the %d keypoint views' pyramids take %d x %d bytes, "
+                "over pyramid_budget_bytes = %d (fewer frames per step, or fewer KPS_AUG views)"
+                % (len(self.kps_views), batch, kept, pyramid_budget_bytes))
+        V, rows = len(self.kps_views), self.mask_rows(batch)
+        K, S = int(cfg.KRCNN.NUM_KEYPOINTS), int(cfg.KRCNN.HEATMAP_SIZE)
+        if V * rows * K * S * S * 4 > heatmap_budget_bytes:
+            raise ValueError(
+                "KeypointAugFramePipeline: the views' heatmaps take %d views x %d rows x "
+                "(%d x %d x %d x 4 = %d) bytes = %d, over heatmap_budget_bytes = %d (fewer "
+                "frames per step, or fewer KPS_AUG views)"
+                % (V, rows, K, S, S, K * S * S * 4, V * rows * K * S * S * 4,
+                   heatmap_budget_bytes))
+
+    def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
+        F = frames.shape[0]
+        flipped = self._flipped_frames(frames)
+        ident = self.kps_views[0]
+        if self.bbox_aug:
+            out, pyrs, views = self._box_pass(frames, flipped, self.kps_views,
+                                              keep_intermediates)
+        else:
+            out, F, pyr, fast, _ = self._detect(frames, keep_intermediates)
+            pyrs, views = {ident: (pyr, fast)}, {}
+        self._body_only(frames, flipped, self.kps_views, pyrs, views, keep_intermediates)
+        if keep_intermediates:
+            out["views"] = views
+        out["_pyrs"] = pyrs
+        out["_kps_keep"] = keep_intermediates
+        keyps, more, out["kps_total"] = self._aug_keypoints(
+            out, out, self.mask_rows(F), 0, views if keep_intermediates else None)
+        out["keyps"], out["kps_rois"] = keyps, more["kps_rois"]
+        if keep_intermediates:
+            out.update(more)
+        self._oks_stage(out, keyps, keep_intermediates)
+        if sync:
+            self.complete(out)
+        return out
+
+    def _aug_keypoints(self, out, src, rows, row0, views=None):
+        """im_detect_keypoints_aug + keypoint_results' decode for rows [row0, row0 + rows)
+        of the keypoint batch of src's detections: every view's heatmaps, then one
+        combine-and-decode launch.  -> (keyps, the kps_* tensors of those rows -- rois
+        and features of the identity view, the combined heatmaps when views is given --
+        and the device total).  views: the keep_intermediates dict, given each view's
+        kps_rois, kps_heatmaps and kps_feat (appended to rows already there)."""
+        cfg = self.cfg
+        dets, dcls, dcnt = src["dets"], src["classes"], src["counts"]
+        F = dets.shape[0]
+        dets_hf = None
+        heats, first = [], None
+        for i, v in enumerate(self.kps_views):
+            g = self.geom[v]
+            d = dets
+            if g.hflip:
+                if dets_hf is None:
+                    dets_hf = self._hflip_dets(dets)
+                d = dets_hf
+            krois, klvl, _, ktotal = ops.mask_rois(
+                d, dcls, dcnt, g.im_scale_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
+                cfg.FPN.ROI_MAX_LEVEL, row0=row0)
+            pyr, fast = out["_pyrs"][v]
+            heat, kfeat = self._keypoint_heatmaps(pyr, krois, klvl, fast)
+            heats.append(heat)
+            if i == 0:
+                first = (krois, kfeat, ktotal)
+            if views is not None:
+                new = dict(kps_rois=krois, kps_heatmaps=heat, kps_feat=kfeat)
+                vd = views.setdefault(v, {})
+                for k, t in new.items():
+                    vd[k] = torch.cat([vd[k], t]) if row0 and k in vd else t
+        # the decode's boxes: the stored detections of the same rows (_keypoint_rows)
+        kboxes = ops.mask_rois(dets, dcls, dcnt, self._ones_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
+                               cfg.FPN.ROI_MAX_LEVEL, row0=row0)[0][:, 1:5]
+        self._mark("im_detect_keypoints")
+        res = ops.heatmaps_to_keypoints_aug(
+            heats, [self.geom[v].hflip for v in self.kps_views], self.kps_ds, self.kps_us,
+            kboxes, cfg.KRCNN.INFERENCE_MIN_SIZE, self.kps_heur, self.kps_area_th,
+            want_combined=views is not None)
+        self._mark("misc_keypoints")
+        keyps, comb = res if views is not None else (res, None)
+        more = {"kps_rois": first[0], "kps_feat": first[1], "kps_boxes": kboxes}
+        if comb is not None:
+            more["kps_heatmaps"] = comb
+        return keyps, more, first[2]
+
+    def _keypoint_overflow(self, out, src, rows, row0):
+        """complete()'s rare rows past the padded batch run through every keypoint view
+        again (out["views"] is there exactly when the step kept its intermediates)."""
+        keyps, more, _ = self._aug_keypoints(out, src, rows, row0, out.get("views"))
+        return keyps, more
+
+    def _raise_on_failed_counts(self, counts):
+        if self.bbox_aug:
+            self._raise_on_failed_union(counts)
+        ops.raise_on_failed_counts(counts)
 
 
 class RaggedBatch:

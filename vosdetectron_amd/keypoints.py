@@ -12,7 +12,11 @@ reference's per-frame numpy loop becomes a score, a rank, a suppression bitmask
 and a greedy pass in one workgroup per frame.  Rows are processed in descending
 mean logit, the higher index first among equal scores; NaN logits are unsupported.
 The pipeline's switch is KeypointFramePipeline(nms_oks=...): the config key
-KRCNN.NMS_OKS itself is still rejected by load_cfg (config.UNSUPPORTED)."""
+KRCNN.NMS_OKS itself is still rejected by load_cfg (config.UNSUPPORTED).
+
+flip_heatmaps (keypoints.py:90-100) is the one-view case of the kernel that combines
+the TEST.KPS_AUG views inside the decode (ops.heatmaps_to_keypoints_aug ->
+vd_heatmaps_to_keypoints_aug, engine.KeypointAugFramePipeline)."""
 from __future__ import annotations
 
 import numpy as np
@@ -36,6 +40,32 @@ def get_keypoints():
 def get_person_class_index():
     """keypoints.py:66-68: index of the person class in COCO."""
     return 1
+
+
+def flip_permutation():
+    """get_keypoints()'s flip map as channel indices: flipped channel k is channel
+    perm[k] (each left keypoint swapped with its right one, the nose kept)."""
+    names, flip = get_keypoints()
+    perm = list(range(len(names)))
+    for left, right in flip.items():
+        l, r = names.index(left), names.index(right)
+        perm[l], perm[r] = r, l
+    return perm
+
+
+def flip_heatmaps(heatmaps, device="cuda"):
+    """keypoints.py:90-100: heatmaps [R,17,M,M] flipped horizontally -- the left/right
+    channels swapped and the last axis reversed -- by the device kernel
+    (vd_heatmaps_to_keypoints_aug with the one view flipped; its combined map is the
+    result).  Tensors in, tensor out; numpy in, numpy out."""
+    h, as_numpy = _as_f32(heatmaps, "heatmaps",
+                          lambda t: t.dim() == 4 and t.shape[1] == len(_KEYPOINTS)
+                          and t.shape[2] == t.shape[3], "R x %d x M x M" % len(_KEYPOINTS))
+    h = _on_device(h, device)
+    boxes = torch.zeros((h.shape[0], 4), dtype=torch.float32, device=h.device)
+    _, flipped = ops.heatmaps_to_keypoints_aug([h], [True], [False], [False], boxes,
+                                               heur="HM_MAX", want_combined=True)
+    return flipped.cpu().numpy() if as_numpy else flipped
 
 
 def heatmaps_to_keypoints(maps, rois, device="cuda"):

@@ -1858,6 +1858,89 @@ def heatmaps_to_keypoints(maps: torch.Tensor, boxes: torch.Tensor,
     return out
 
 
+KPS_AUG_HEURS = {"HM_AVG": 0, "HM_MAX": 1}  # include/vosdet.h VD_KPS_AUG_*
+KPS_AUG_MAX_VIEWS = 32
+
+
+def _bits(flags, name, V):
+    flags = [bool(f) for f in flags]
+    if len(flags) != V:
+        raise ValueError("%s: %d flags for %d views" % (name, len(flags), V))
+    return sum(1 << i for i, f in enumerate(flags) if f)
+
+
+def heatmaps_to_keypoints_aug(views, hflips, ds, us, boxes: torch.Tensor, min_size: int = 0,
+                              heur: str = "HM_AVG", area_th=None, flip_perm=None,
+                              want_combined: bool = False):
+    """im_detect_keypoints_aug's combination (lib/core/test.py:630-651, 705-730) and
+    keypoint_results' decode in one launch (vd_heatmaps_to_keypoints_aug).  views: the
+    V <= 32 views' [R,K,M,M] fp32 logits as the network returned them, in heatmaps_ts
+    order (the identity view first); hflips / ds / us: per view, whether it saw the
+    flipped image (read as flip_heatmaps inverts it) and whether its scale is below /
+    above TEST.SCALE; boxes [R,>=4]: the unflipped detection boxes; heur HM_AVG /
+    HM_MAX; area_th: None, or KPS_AUG.AREA_TH for SCALE_SIZE_DEP (a box with
+    area < area_th drops the ds views, any other the us views).  flip_perm: K channel
+    indices, by default keypoints.get_keypoints()'s left/right swap when K == 17.
+    -> [R,4,K] rows (x, y, logit, prob), or (that, the combined [R,K,M,M] maps) with
+    want_combined.  No host read."""
+    views = list(views)
+    V = len(views)
+    if V < 1 or V > KPS_AUG_MAX_VIEWS:
+        raise ValueError("heatmaps_to_keypoints_aug: %d views (1..%d)" % (V, KPS_AUG_MAX_VIEWS))
+    ms = [_need(v, "views[%d]" % i) for i, v in enumerate(views)]
+    m = ms[0]
+    if m.dim() != 4 or m.shape[2] != m.shape[3]:
+        raise ValueError("views must be R x K x M x M, got %s" % (tuple(m.shape),))
+    for i, v in enumerate(ms):
+        if v.shape != m.shape or v.device != m.device:
+            raise ValueError("views[%d] is %s on %s, views[0] %s on %s"
+                             % (i, tuple(v.shape), v.device, tuple(m.shape), m.device))
+    R, K, M = m.shape[0], m.shape[1], m.shape[2]
+    if M < 1 or M > KEYPOINT_MAX_HEATMAP or K < 1 or K > KEYPOINT_MAX_K:
+        raise ValueError("heatmaps_to_keypoints_aug: M = %d (<= %d), K = %d (<= %d)"
+                         % (M, KEYPOINT_MAX_HEATMAP, K, KEYPOINT_MAX_K))
+    if heur not in KPS_AUG_HEURS:
+        raise ValueError("heatmaps_to_keypoints_aug: heur %r not in %s"
+                         % (heur, sorted(KPS_AUG_HEURS)))
+    hf, dsb, usb = _bits(hflips, "hflips", V), _bits(ds, "ds", V), _bits(us, "us", V)
+    if (dsb | usb) & 1 or dsb & usb:
+        raise ValueError("heatmaps_to_keypoints_aug: the identity view carries no ds / us tag "
+                         "and no view carries both (ds %s, us %s)" % (list(ds), list(us)))
+    if flip_perm is None:
+        if K != 17:
+            raise ValueError("heatmaps_to_keypoints_aug: K = %d needs an explicit flip_perm "
+                             "(the default is the 17 COCO keypoints' left/right swap)" % K)
+        from .keypoints import flip_permutation
+        flip_perm = flip_permutation()
+    perm = [int(p) for p in flip_perm]
+    if len(perm) != K or any(p < 0 or p >= K for p in perm):
+        raise ValueError("flip_perm must hold K = %d indices in [0, %d), got %s" % (K, K, perm))
+    th = -1.0
+    if area_th is not None:
+        th = float(area_th)
+        if not th >= 0 or float(np.float32(th)) != th:
+            raise ValueError("area_th = %r must be a non-negative number that float32 holds "
+                             "exactly" % (area_th,))
+    if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda or boxes.dtype != torch.float32:
+        raise TypeError("boxes must be a float32 device tensor")
+    if boxes.dim() != 2 or boxes.shape[0] != R or boxes.shape[1] < 4:
+        raise ValueError("boxes must be R x >=4, got %s" % (tuple(boxes.shape),))
+    b = boxes
+    if b.stride(1) != 1 or (R > 1 and b.stride(0) < 4):
+        b = b.contiguous()
+    stride = b.stride(0) if R > 1 else 4
+    out = torch.empty((R, 4, K), dtype=torch.float32, device=m.device)
+    comb = torch.empty_like(m) if want_combined else None
+    if R > 0:
+        ptrs = (ctypes.c_void_p * V)(*[v.data_ptr() for v in ms])
+        cperm = (ctypes.c_int32 * K)(*perm)
+        check(lib().vd_heatmaps_to_keypoints_aug(
+            ptrs, V, hf, dsb, usb, cperm, KPS_AUG_HEURS[heur], th, R, K, M, b.data_ptr(),
+            int(stride), int(min_size), comb.data_ptr() if want_combined else None,
+            out.data_ptr(), _stream()), "vd_heatmaps_to_keypoints_aug")
+    return (out, comb) if want_combined else out
+
+
 # --------------------------------------------------------------------------- #
 # keypoint_results: OKS NMS                                                    #
 # --------------------------------------------------------------------------- #
