@@ -116,10 +116,10 @@ def test_mask_overflow_complete(graph_setup, monkeypatch):
     assert sum(ref["counts_host"]) > 64, ref["counts_host"]
     monkeypatch.setattr(pipe, "mask_rows", lambda F: 64)
     out = pipe.run(frames, sync=False)
-    assert out["masks"].shape[0] == 64 and "_pyr" in out
+    assert out["masks"].shape[0] == 64 and "_pyrs" in out
     out = pipe.complete(out)
     torch.cuda.synchronize()
-    assert "_pyr" not in out and "_fast" not in out
+    assert "_pyrs" not in out
     assert out["counts_host"] == ref["counts_host"]
     for k in ("dets", "classes", "counts", "mask_rois", "mask_feat"):
         assert torch.equal(out[k], ref[k]), k

@@ -466,9 +466,9 @@ def test_row_ranges_give_identical_tensors(step, world):
     out = pipe.run(frames, sync=False)
     rows = pipe.mask_rows(2)
     assert rows % 128 == 0
-    k_all, more_all, total = pipe._aug_keypoints(out, out, rows, 0)
-    a = pipe._aug_keypoints(out, out, rows // 2, 0)
-    b = pipe._aug_keypoints(out, out, rows // 2, rows // 2)
+    k_all, more_all, total = pipe._keypoints(out, out, rows, 0)
+    a = pipe._keypoints(out, out, rows // 2, 0)
+    b = pipe._keypoints(out, out, rows // 2, rows // 2)
     M = int(total.item())
     assert M == sum(eager["counts_host"]) and M > 1
     assert torch.equal(torch.cat([a[0], b[0]]), k_all)
@@ -476,7 +476,7 @@ def test_row_ranges_give_identical_tensors(step, world):
         assert torch.equal(torch.cat([a[1][k], b[1][k]]), more_all[k]), k
     assert torch.equal(k_all, out["keyps"]) and torch.equal(k_all[:M], eager["keyps"])
     # a range that starts inside the real rows: the overflow batch's shape
-    c = pipe._aug_keypoints(out, out, 64, M - 1)
+    c = pipe._keypoints(out, out, 64, M - 1)
     assert torch.equal(c[0][:1], eager["keyps"][M - 1:])
     pipe.complete(out)
 

@@ -331,6 +331,33 @@ def test_pipeline_graph_replay_with_oks(oks_setup):
             assert torch.equal(out[k], eager[k]), k
 
 
+def test_complete_runs_the_rows_past_the_padded_batch_with_oks(oks_setup, monkeypatch):
+    """A padded batch shorter than the detections, with nms_oks: complete() decodes the
+    rest and runs the NMS again on the full set.  The pre-NMS rows are the full run's;
+    the result is ops.nms_oks_frames of this run's own pre-NMS tensors, whatever
+    algorithm the head's deconvolution picks for the other batch size."""
+    from vosdetectron_amd import ops
+    s = oks_setup
+    pipe, full = s["pipe"], s["out"]
+    M = sum(full["counts_pre_oks_host"])
+    cap = 64 if M > 64 else M // 2
+    assert 0 < cap < M
+    monkeypatch.setattr(pipe, "mask_rows", lambda F: cap)
+    out = pipe.run(s["frames"], keep_intermediates=True, sync=False)
+    assert out["kps_rois"].shape[0] == cap and "counts_host" not in out
+    pipe.complete(out)
+    assert out["counts_pre_oks_host"] == full["counts_pre_oks_host"]
+    for k in ("dets_pre_oks", "classes_pre_oks", "kps_rois"):
+        assert torch.equal(out[k], full[k]), k
+    assert out["keyps_pre_oks"].shape == full["keyps_pre_oks"].shape
+    res = ops.nms_oks_frames(out["keyps_pre_oks"], out["dets_pre_oks"], out["classes_pre_oks"],
+                             out["counts_pre_oks"], pipe.oks_thresh)
+    assert out["counts_host"] == res.counts.cpu().tolist()
+    assert torch.equal(out["dets"], res.dets) and torch.equal(out["classes"], res.classes)
+    assert torch.equal(out["counts"], res.counts) and torch.equal(out["oks_keep"], res.keep)
+    assert torch.equal(out["keyps"], res.keyps[:sum(out["counts_host"])])
+
+
 def test_gather_of_the_post_nms_result(oks_setup):
     """No process group: the send slot is the result."""
     from vosdetectron_amd.runner import ResultGatherer, frame_keyps

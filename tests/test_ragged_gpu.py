@@ -199,7 +199,7 @@ def test_ragged_engine_stagewise(ragged_setup):
     against the oracle on the GPU's own upstream tensors, RoIAlign within 1e-4."""
     cfg, model, sd, pipe, frames, batch, out = ragged_setup
     assert out["frame_hw"] == SET_A and tuple(out["feats"][-1].shape[-2:]) == (104, 104)
-    assert "_im_scale_d" not in out and "_pyr" not in out
+    assert "_pyrs" not in out
     for f, fr in enumerate(frames):
         stagewise(cfg, pipe, out, fr, f)
         k = out["counts_host"][f]

@@ -440,6 +440,44 @@ def test_pipeline_async_equals_sync(tta):
             assert torch.equal(o2[k], out[k]), k
 
 
+def test_complete_runs_the_rows_past_the_padded_mask_batch(tta, monkeypatch):
+    """A padded mask batch shorter than the detections: complete() sends the rest through
+    every mask view again, and the per-view intermediates grow with them.  Both layouts:
+    the completed step passes the stage-wise checks on its own tensors, over all M rows.
+    channels_last (where two runs of the body agree bit for bit, see above): detections,
+    mask RoIs and mask RoI features are the full run's, the masks within 1e-5 (the mask
+    head's GEMM may pick another algorithm for the other batch size)."""
+    cfg, model, sd, pipe, frames, ref = tta
+    M = sum(ref["counts_host"])
+    cap = 64 if M > 64 else M // 2
+    assert 0 < cap < M
+    monkeypatch.setattr(pipe, "mask_rows", lambda F: cap)
+    out = pipe.run(_t(frames), keep_intermediates=True, sync=False)
+    assert out["masks"].shape[0] == cap and "_pyrs" in out
+    pipe.complete(out)
+    assert "_pyrs" not in out
+    rows = sum(out["counts_host"])
+    assert rows > cap
+    for k in ("masks", "mask_rois", "mask_feat"):
+        assert out[k].shape[0] == rows, k
+    for v in pipe.mask_views:
+        for k in ("masks", "mask_rois"):
+            assert out["views"][v][k].shape[0] == rows, (v, k)
+    _check_detections(cfg, pipe, out)
+    _check_masks(pipe, out)
+    if pipe.channels_last:
+        assert out["counts_host"] == ref["counts_host"]
+        for k in ("dets", "classes", "counts", "mask_rois", "mask_feat"):
+            assert torch.equal(out[k], ref[k]), k
+        assert out["masks"].shape == ref["masks"].shape
+        assert float((out["masks"] - ref["masks"]).abs().max()) <= 1e-5
+        for v in pipe.mask_views:
+            o, r = out["views"][v], ref["views"][v]
+            assert torch.equal(o["mask_rois"], r["mask_rois"]), v
+            assert o["masks"].shape == r["masks"].shape
+            assert float((o["masks"] - r["masks"]).abs().max()) <= 1e-5, v
+
+
 def test_pipeline_without_aug_is_frame_pipeline(tta):
     """Both AUG keys off: the identity view alone through the union and mask-combine
     kernels is FramePipeline's step bit for bit -- vd_box_detections on the run's own

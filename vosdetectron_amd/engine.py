@@ -27,9 +27,13 @@ KeypointFramePipeline(nms_oks=...) adds keypoint_results' OKS NMS (vd_nms_oks_fr
 KeypointAugFramePipeline runs the keypoint configs with TEST.BBOX_AUG / TEST.KPS_AUG
 (im_detect_keypoints_aug, test.py:567-730): vd_heatmaps_to_keypoints_aug combines the
 views' heatmaps inside the decode.
+
+All of them run FramePipeline._run -- box pass, heads over the head views, complete() --
+and override the part they change (see FramePipeline; C4FramePipeline has its own _run).
 """
 from __future__ import annotations
 
+import copy
 import math
 
 import numpy as np
@@ -70,52 +74,80 @@ def nms_options(cfg) -> dict:
     return opts
 
 
+class _ViewGeom:
+    """Blob geometry of frames of one size at one view (scale, max_size, hflip), the
+    identity view of a plain step or a test-time-augmentation view (lib/utils/blob.py:
+    37-161): get_target_scale, cv2.resize to round(H*s) x round(W*s) (done on the device
+    when s != 1), pad to `stride` (get_max_shape), and the per-frame rows the proposal,
+    detection and RoI kernels read -- the fields a RaggedBatch carries per frame."""
+
+    def __init__(self, view, H, W, stride, F, device):
+        self.view, self.F = view, F
+        self.hflip = bool(view[2])
+        self.scale = ops.target_scale(H, W, view[0], view[1])
+        self.Hr, self.Wr = ops.resized_hw(H, W, self.scale)
+        self.Hp = int(math.ceil(self.Hr / stride) * stride)
+        self.Wp = int(math.ceil(self.Wr / stride) * stride)
+        self.im_info = torch.tensor([[self.Hp, self.Wp, self.scale]] * F, dtype=torch.float32,
+                                    device=device)
+        self.im_scale_t = torch.full((F,), self.scale, dtype=torch.float32, device=device)
+        self.im_scale_d = torch.full((F,), self.scale, dtype=torch.float64, device=device)
+        self.im_hw = torch.tensor([[H, W]] * F, dtype=torch.int32, device=device)
+
+    def rows(self, F):
+        """The geometry of a step of F <= batch frames."""
+        if F == self.F:
+            return self
+        g = copy.copy(self)
+        g.F = F
+        for k in ("im_info", "im_scale_t", "im_scale_d", "im_hw"):
+            setattr(g, k, getattr(self, k)[:F])
+        return g
+
+
 class FramePipeline:
+    """The step every pipeline here runs (_run): the box pass (_box_pass: body, box
+    stages, detections; leaves each head view's geometry and pyramid in out["_pyrs"]),
+    the per-detection heads (_roi_heads) over the head views (_view_rois), and
+    complete().  A subclass overrides the part it changes."""
     ASYNC = True  # run(sync=False) queues a step with no host read (see run())
+    KEYPOINTS = False  # the class runs the MODEL.KEYPOINTS_ON configs
+    TEST_AUG = ()  # which of TEST.BBOX_AUG / MASK_AUG / KPS_AUG the class serves
+    mask_heur = None  # one mask view, no combination
+
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
                  det_cap=256, device="cuda"):
         self._setup(model, cfg, batch, channels_last, det_cap, device)
         self.H, self.W = frame_hw
-        # blob geometry (lib/utils/blob.py:37-161): get_target_scale, cv2.resize
-        # to round(H*s) x round(W*s) (done on the device when s != 1), pad to
-        # FPN.COARSEST_STRIDE (get_max_shape; the C4 pipeline does not pad)
-        scale = ops.target_scale(self.H, self.W, cfg.TEST.SCALE, cfg.TEST.MAX_SIZE)
-        self.im_scale = scale
-        self.Hr, self.Wr = ops.resized_hw(self.H, self.W, scale)
-        st = cfg.FPN.COARSEST_STRIDE
-        self.Hp = int(math.ceil(self.Hr / st) * st)
-        self.Wp = int(math.ceil(self.Wr / st) * st)
-        F = batch
-        self.im_info = torch.tensor([[self.Hp, self.Wp, scale]] * F, dtype=torch.float32,
-                                    device=self.device)
-        self.im_scale_t = torch.full((F,), scale, dtype=torch.float32, device=self.device)
-        self.im_scale_d = torch.full((F,), scale, dtype=torch.float64, device=self.device)
-        self.im_hw = torch.tensor([[self.H, self.W]] * F, dtype=torch.int32, device=self.device)
+        # the identity view's geometry (the C4 pipeline, which does not pad, overwrites
+        # Hp, Wp and im_info)
+        g = self.ident = _ViewGeom(self.head_views[0], self.H, self.W, cfg.FPN.COARSEST_STRIDE,
+                                   batch, self.device)
+        self.im_scale, self.Hr, self.Wr, self.Hp, self.Wp = g.scale, g.Hr, g.Wr, g.Hp, g.Wp
+        self.im_info, self.im_scale_t, self.im_scale_d = g.im_info, g.im_scale_t, g.im_scale_d
+        self.im_hw = g.im_hw
 
     def _setup(self, model, cfg, batch, channels_last, det_cap, device):
         """Everything of the constructor that does not depend on the frame size."""
-        if cfg.MODEL.KEYPOINTS_ON and not isinstance(self, KeypointFramePipeline):
+        tst, name = cfg.TEST, type(self).__name__
+        if cfg.MODEL.KEYPOINTS_ON and not self.KEYPOINTS:
             raise NotImplementedError(
                 "%s: MODEL.KEYPOINTS_ON configs run on KeypointFramePipeline (FPN, frames of "
-                "one size); ragged, C4 and VOS keypoint steps are not built"
-                % type(self).__name__)
-        if (cfg.TEST.BBOX_AUG.ENABLED or cfg.TEST.KPS_AUG.ENABLED) \
-                and isinstance(self, KeypointFramePipeline) \
-                and not isinstance(self, KeypointAugFramePipeline):
+                "one size); ragged, C4 and VOS keypoint steps are not built" % name)
+        if (tst.BBOX_AUG.ENABLED or tst.KPS_AUG.ENABLED) and self.KEYPOINTS \
+                and "KPS_AUG" not in self.TEST_AUG:
             raise NotImplementedError(
                 "%s: TEST.BBOX_AUG / TEST.KPS_AUG on a keypoint config run on "
-                "KeypointAugFramePipeline (FPN, frames of one size)" % type(self).__name__)
-        if (cfg.TEST.BBOX_AUG.ENABLED or cfg.TEST.MASK_AUG.ENABLED) \
-                and not isinstance(self, (AugFramePipeline, KeypointAugFramePipeline)):
+                "KeypointAugFramePipeline (FPN, frames of one size)" % name)
+        if (tst.BBOX_AUG.ENABLED or tst.MASK_AUG.ENABLED) and not self.TEST_AUG:
             raise NotImplementedError(
                 "%s: TEST.BBOX_AUG / TEST.MASK_AUG run on AugFramePipeline (FPN mask configs, "
                 "frames of one size) and, for keypoint configs, on KeypointAugFramePipeline; "
-                "ragged, C4 and VOS steps with test-time augmentation are not built"
-                % type(self).__name__)
-        if cfg.TEST.KPS_AUG.ENABLED and not isinstance(self, KeypointAugFramePipeline):
+                "ragged, C4 and VOS steps with test-time augmentation are not built" % name)
+        if tst.KPS_AUG.ENABLED and "KPS_AUG" not in self.TEST_AUG:
             raise NotImplementedError(
                 "%s: TEST.KPS_AUG runs on KeypointAugFramePipeline (FPN keypoint configs, "
-                "frames of one size)" % type(self).__name__)
+                "frames of one size)" % name)
         if not cfg.MODEL.KEYPOINTS_ON and not hasattr(model, "Mask_Head"):
             raise NotImplementedError(
                 "%s: the model has no Mask_Head (MODEL.MASK_ON False); a box-only step is "
@@ -127,6 +159,8 @@ class FramePipeline:
         self.channels_last = channels_last
         self.det_cap = det_cap
         self._nms_options = nms_options(cfg)
+        # the views whose pyramids the heads read: here the identity view alone
+        self.head_views = [(tst.SCALE, tst.MAX_SIZE, False)]
         self.lut = torch.from_numpy(ops.pixel_lut(cfg.PIXEL_MEANS)).to(self.device)
         if cfg.FPN.FPN_ON:
             k_min, k_max = cfg.FPN.RPN_MIN_LEVEL, cfg.FPN.RPN_MAX_LEVEL
@@ -167,25 +201,25 @@ class FramePipeline:
         """{stage: average seconds per call} (Timer.average_time of the reference)."""
         return {k: v.average_time for k, v in (self.timers or {}).items()}
 
-    def make_blob(self, frames):
-        """get_image_blob on the device: identity scale -> vd_image_to_blob, else
-        vd_image_resize_to_blob (mean subtraction + INTER_LINEAR resize + pad)."""
+    def make_blob(self, frames, g=None):
+        """get_image_blob on the device at view geometry g (None: the pipeline's own):
+        identity scale -> vd_image_to_blob, else vd_image_resize_to_blob (mean
+        subtraction + INTER_LINEAR resize + pad)."""
         nhwc = self.channels_last
-        if self.im_scale == 1.0:
-            blob = ops.image_to_blob(frames, self.lut, self.Hp, self.Wp, nhwc=nhwc)
+        scale, Hp, Wp = (self.im_scale, self.Hp, self.Wp) if g is None else (g.scale, g.Hp, g.Wp)
+        if scale == 1.0:
+            blob = ops.image_to_blob(frames, self.lut, Hp, Wp, nhwc=nhwc)
         else:
-            blob = ops.image_resize_to_blob(frames, self.lut, self.im_scale, self.Hp, self.Wp,
-                                            nhwc=nhwc)
+            blob = ops.image_resize_to_blob(frames, self.lut, scale, Hp, Wp, nhwc=nhwc)
         return blob.permute(0, 3, 1, 2) if nhwc else blob  # NCHW view
 
     def backbone(self, frames):
         return self.model.Conv_Body(self.make_blob(frames))  # [P6, P5, P4, P3, P2]
 
     def _frame_rows(self, frames):
-        """(F, im_info, im_scale fp32, im_scale fp64, im_hw) of a step's frames: the
-        per-frame rows the proposal, detection and mask-RoI kernels read."""
-        F = frames.shape[0]
-        return F, self.im_info[:F], self.im_scale_t[:F], self.im_scale_d[:F], self.im_hw[:F]
+        """The geometry a step's frames run at: F, im_info, im_scale_t (fp32), im_scale_d
+        (fp64) and im_hw, the per-frame rows the proposal, detection and RoI kernels read."""
+        return self.ident.rows(frames.shape[0])
 
     def nhwc_pyramid(self, feats):
         """P2..P5 as B x H x W x C (a free view when the body ran channels_last)."""
@@ -218,27 +252,26 @@ class FramePipeline:
                 self._collect_marks()
 
     def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
-        out, F, pyr, fast, im_scale_d = self._detect(frames, keep_intermediates)
-        self._roi_heads(out, F, pyr, fast, im_scale_d, keep_intermediates)
+        out = self._box_pass(frames, keep_intermediates)
+        self._roi_heads(out, keep_intermediates)
         if sync:
             self.complete(out)
         return out
 
-    def _detect(self, frames: torch.Tensor, keep_intermediates: bool = False):
+    def _box_pass(self, frames: torch.Tensor, keep_intermediates: bool = False):
         """im_detect_bbox and box_results_with_nms_and_limit of one step: the body, the
-        box stages and the detections.  -> (out, F, NHWC pyramid, fast, im_scale fp64)."""
-        cfg = self.cfg
-        F, im_info, im_scale_t, im_scale_d, im_hw = self._frame_rows(frames)
+        box stages and the detections.  -> out; out["_pyrs"] holds, per head view, (the
+        step's geometry, the NHWC pyramid, fast)."""
+        cfg, tst = self.cfg, self.cfg.TEST
+        g = self._frame_rows(frames)
         feats = self.backbone(frames)
         self._mark("conv_body")
-        tst = cfg.TEST
         rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post = \
-            self._box_stages(feats, im_info)
-        K = cls_prob.shape[1]
-        bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
+            self._box_stages(feats, g.im_info)
+        F, K = g.F, cls_prob.shape[1]
         dets, dcls, dcnt = ops.box_detections(
             rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
-            im_scale_t, im_hw, tst.SCORE_THRESH, tst.NMS,
+            g.im_scale_t, g.im_hw, tst.SCORE_THRESH, tst.NMS,
             tst.DETECTIONS_PER_IM, cfg.MODEL.BBOX_REG_WEIGHTS, self.det_cap,
             nms_cross_class=tst.NMS_CROSS_CLASS, num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE,
             **self._nms_options)
@@ -248,13 +281,20 @@ class FramePipeline:
                "cls_prob": cls_prob, "bbox_pred": bbox_pred}
         if keep_intermediates:  # for stage-wise parity tests
             out.update(feats=feats, rpn_probs=probs, rpn_deltas=deltas, pyramid=pyr)
-        return out, F, pyr, fast, im_scale_d
+        # the pyramid stays referenced only until complete() (the rare overflow batch
+        # reads it); complete() drops it so a kept result does not pin ~1.5 GB
+        out["_pyrs"] = {self.head_views[0]: (g, pyr, fast)}
+        return out
+
+    def _nhwc_heads(self):
+        """The heads take the RoI features as NHWC (the body ran channels_last)."""
+        return self.channels_last and getattr(self.model.Box_Head, "nhwc_ready", False)
 
     def _box_stages(self, feats, im_info):
         """im_detect_bbox's stages between the body and the decode, for the frames
         whose blob geometry im_info holds: RPN heads, proposals, collect, box RoIAlign
-        and the box head.  -> (rois, roi counts, cls_prob, bbox_pred (as Box_Outs
-        returns it), RPN probs, RPN deltas, NHWC pyramid, fast, post)."""
+        and the box head.  -> (rois, roi counts, cls_prob, the per-class bbox_pred,
+        RPN probs, RPN deltas, NHWC pyramid, fast, post)."""
         cfg = self.cfg
         # RPN heads on P2..P6 (finest first for the proposal kernel)
         probs, deltas = [], []
@@ -274,7 +314,7 @@ class FramePipeline:
         pyr = self.nhwc_pyramid(feats)
         fr = cfg.FAST_RCNN
         flat_rois, flat_lvl = rois.view(-1, 5), rlvl.view(-1)
-        fast = self.channels_last and getattr(self.model.Box_Head, "nhwc_ready", False)
+        fast = self._nhwc_heads()
         box_feat = ops.roi_align_fpn(pyr, self.roi_scales, flat_rois, flat_lvl,
                                      fr.ROI_XFORM_RESOLUTION, fr.ROI_XFORM_SAMPLING_RATIO,
                                      roi_order=ops.xcd_roi_order(flat_rois, flat_lvl),
@@ -282,26 +322,8 @@ class FramePipeline:
         x = self.model.Box_Head.mlp_nhwc(box_feat) if fast else self.model.Box_Head.mlp(box_feat)
         cls_prob, bbox_pred = self.model.Box_Outs(x)
         self._mark("box_head")
+        bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, cls_prob.shape[1])
         return rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post
-
-    def _roi_heads(self, out, F, pyr, fast, im_scale_d, keep_intermediates):
-        """The per-detection heads after misc_bbox: here im_detect_mask."""
-        cfg = self.cfg
-        dets, dcls, dcnt = out["dets"], out["classes"], out["counts"]
-        # the mask batch: F x DETECTIONS_PER_IM rows (padded to 64), built on the
-        # device from the device counts -- no host read inside the step
-        # (box_results_with_nms_and_limit keeps <= DETECTIONS_PER_IM per frame
-        # barring exact score ties at the limit; complete() runs the rest)
-        cap = self.mask_rows(F)
-        mrois, mlvl, mcls, mtotal = ops.mask_rois(
-            dets, dcls, dcnt, im_scale_d, cap, cfg.FPN.ROI_MIN_LEVEL,
-            cfg.FPN.ROI_MAX_LEVEL)
-        out["masks"], out["mask_feat"] = self._mask_batch(pyr, mrois, mlvl, mcls, fast)
-        out["mask_rois"], out["mask_total"] = mrois, mtotal
-        # the pyramid stays referenced only until complete() (the rare overflow
-        # batch reads it); complete() drops it so a kept result does not pin ~1.5 GB
-        out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
-        self._mark("im_detect_mask")
 
     def _post_detections(self, dets, classes, counts):
         """Hook after box_results_with_nms_and_limit's device steps (the VOS loop
@@ -312,47 +334,127 @@ class FramePipeline:
         (a handful of stable shapes for the convolution algorithm search)."""
         return -(-F * int(self.cfg.TEST.DETECTIONS_PER_IM) // 64) * 64
 
+    def _hflip_dets(self, dets):
+        """flip_boxes of the detections, float32: x1' = (W - x2) - 1."""
+        dets_hf = dets.clone()
+        dets_hf[..., 0] = self.W - dets[..., 2] - 1
+        dets_hf[..., 2] = self.W - dets[..., 0] - 1
+        return dets_hf
+
+    def _view_rois(self, out, src, rows, row0=0):
+        """Rows [row0, row0 + rows) of the RoI batch of src's detections (dets, classes,
+        counts), once per head view: yields (view, (RoIs at the view's scale, levels,
+        classes, device total), pyramid, fast).  The batch is F x DETECTIONS_PER_IM rows
+        built on the device from the device counts -- no host read inside the step; a
+        flipped view takes flip_boxes of the detections, made once."""
+        cfg = self.cfg
+        dets, dcls, dcnt = src["dets"], src["classes"], src["counts"]
+        dets_hf = None
+        for v in self.head_views:
+            g, pyr, fast = out["_pyrs"][v]
+            if v[2] and dets_hf is None:
+                dets_hf = self._hflip_dets(dets)
+            yield v, ops.mask_rois(dets_hf if v[2] else dets, dcls, dcnt, g.im_scale_d, rows,
+                                   cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL, row0=row0), \
+                pyr, fast
+
+    @staticmethod
+    def _keep_view_rows(views, v, row0, **rows):
+        """keep_intermediates: a head view's per-row tensors into out["views"][v],
+        appended to the rows already there when complete() runs rows past the batch."""
+        if views is not None:
+            vd = views.setdefault(v, {})
+            for k, t in rows.items():
+                vd[k] = torch.cat([vd[k], t]) if row0 and k in vd else t
+
+    def _roi_head(self, pyr, rois, lvl, fast, head, rc, nhwc_fn, nchw_fn):
+        """RoIAlign at rc's resolution (cfg.MRCNN / cfg.KRCNN) in the layout `head` takes,
+        then the head: -> (nhwc_fn or nchw_fn of the RoI features, the features as NCHW)."""
+        if fast and getattr(head, "nhwc_ready", False):
+            feat = ops.roi_align_fpn(pyr, self.roi_scales, rois, lvl, rc.ROI_XFORM_RESOLUTION,
+                                     rc.ROI_XFORM_SAMPLING_RATIO, out_layout="nhwc")
+            return nhwc_fn(feat), feat.permute(0, 3, 1, 2)
+        feat = ops.roi_align_fpn(pyr, self.roi_scales, rois, lvl, rc.ROI_XFORM_RESOLUTION,
+                                 rc.ROI_XFORM_SAMPLING_RATIO)
+        return nchw_fn(feat), feat
+
     def _mask_batch(self, pyr, mrois, mlvl, mcls, fast):
         """Mask RoIAlign + mask head + class-selected masks for a padded batch
         (padding rows are zero boxes whose outputs are never read)."""
-        mc = self.cfg.MRCNN
-        if fast and getattr(self.model.Mask_Head, "nhwc_ready", False):
-            mfeat = ops.roi_align_fpn(pyr, self.roi_scales, mrois, mlvl, mc.ROI_XFORM_RESOLUTION,
-                                      mc.ROI_XFORM_SAMPLING_RATIO, out_layout="nhwc")
-            masks = self.model.Mask_Head.masks_nhwc(mfeat, self.model.Mask_Outs, mcls)
-            return masks, mfeat.permute(0, 3, 1, 2)
-        mfeat = ops.roi_align_fpn(pyr, self.roi_scales, mrois, mlvl, mc.ROI_XFORM_RESOLUTION,
-                                  mc.ROI_XFORM_SAMPLING_RATIO)
-        mh = self.model.Mask_Head.head(mfeat)
-        return self.model.Mask_Outs.selected(mh, mcls), mfeat
+        head, outs = self.model.Mask_Head, self.model.Mask_Outs
+        return self._roi_head(pyr, mrois, mlvl, fast, head, self.cfg.MRCNN,
+                              lambda x: head.masks_nhwc(x, outs, mcls),
+                              lambda x: outs.selected(head.head(x), mcls))
+
+    def _masks(self, out, rows, row0=0):
+        """im_detect_mask, or im_detect_mask_aug, for rows [row0, row0 + rows) of the mask
+        batch: every head view's masks, combined by mask_heur where the class has one.
+        -> (masks, the identity view's mask_rois and mask_feat, the device total)."""
+        views, heur = out.get("views"), self.mask_heur
+        acc = first = None
+        for i, (v, (mrois, mlvl, mcls, mtotal), pyr, fast) in enumerate(
+                self._view_rois(out, out, rows, row0)):
+            masks, mfeat = self._mask_batch(pyr, mrois, mlvl, mcls, fast)
+            if i == 0:
+                first = (mrois, mfeat, mtotal)
+            if heur is None:
+                acc = masks
+            else:
+                masks = masks.contiguous()
+                if i == 0:
+                    acc = torch.empty_like(masks)
+                ops.mask_aug_accumulate(acc, masks, v[2], heur, first=i == 0)
+            self._keep_view_rows(views, v, row0, mask_rois=mrois, masks=masks)
+        if heur is not None:
+            ops.mask_aug_finish(acc, len(self.head_views), heur)
+        return (acc,) + first
+
+    def _roi_heads(self, out, keep_intermediates):
+        """The per-detection heads after misc_bbox: here im_detect_mask
+        (box_results_with_nms_and_limit keeps <= DETECTIONS_PER_IM per frame barring
+        exact score ties at the limit; complete() runs the rest)."""
+        out["masks"], out["mask_rois"], out["mask_feat"], out["mask_total"] = \
+            self._masks(out, self.mask_rows(out["dets"].shape[0]))
+        self._mark("im_detect_mask")
+
+    def _raise_on_failed_counts(self, counts):
+        ops.raise_on_failed_counts(counts)
+
+    def _check_counts(self, counts):
+        """complete()'s checks of the host counts: a failed frame, more than det_cap."""
+        self._raise_on_failed_counts(counts)
+        if max(counts, default=0) > self.det_cap:
+            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
+
+    @staticmethod
+    def _finish_rows(out, keys, M):
+        """complete()'s end: the kept pyramids dropped, out[keys] and the head views'
+        per-row intermediates trimmed to the M real rows."""
+        out.pop("_pyrs", None)
+        for k in keys:
+            out[k] = out[k][:M]
+        for vd in out.get("views", {}).values():
+            for k in ("mask_rois", "masks", "kps_rois", "kps_heatmaps", "kps_feat"):
+                if k in vd:
+                    vd[k] = vd[k][:M]
 
     def complete(self, out: dict) -> dict:
         """The step's one host read, after everything is queued: the detection
         counts (failure / capacity checks), the masks of detections beyond the
-        padded batch (exact score ties at DETECTIONS_PER_IM), and the outputs
-        trimmed to the M = sum(counts) real detections.  Idempotent."""
+        padded batch (exact score ties at DETECTIONS_PER_IM), through every head view
+        again, and the outputs trimmed to the M = sum(counts) real detections.
+        Idempotent."""
         if "counts_host" in out:
             return out
         counts = out["counts"].cpu().tolist()
-        ops.raise_on_failed_counts(counts)
-        if max(counts, default=0) > self.det_cap:
-            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
+        self._check_counts(counts)
+        keys = ("masks", "mask_rois", "mask_feat")
         M, cap = sum(counts), out["masks"].shape[0]
         if M > cap:  # rows [cap, M): a second, rare batch
-            extra = -(-(M - cap) // 64) * 64
-            r2, l2, c2, _ = ops.mask_rois(out["dets"], out["classes"], out["counts"],
-                                          out["_im_scale_d"], extra, self.cfg.FPN.ROI_MIN_LEVEL,
-                                          self.cfg.FPN.ROI_MAX_LEVEL, row0=cap)
-            m2, f2 = self._mask_batch(out["_pyr"], r2, l2, c2, out["_fast"])
-            out["masks"] = torch.cat([out["masks"], m2])
-            out["mask_feat"] = torch.cat([out["mask_feat"], f2])
-            out["mask_rois"] = torch.cat([out["mask_rois"], r2])
-        out.pop("_pyr", None)
-        out.pop("_fast", None)
-        out.pop("_im_scale_d", None)
-        out["masks"] = out["masks"][:M]
-        out["mask_feat"] = out["mask_feat"][:M]
-        out["mask_rois"] = out["mask_rois"][:M]
+            more = self._masks(out, -(-(M - cap) // 64) * 64, cap)
+            for k, t in zip(keys, more):
+                out[k] = torch.cat([out[k], t])
+        self._finish_rows(out, keys, M)
         out["counts_host"] = counts
         return out
 
@@ -382,6 +484,8 @@ class KeypointFramePipeline(FramePipeline):
     pre-NMS indices (-1 past the count).  kps_rois, kps_heatmaps, kps_feat and
     kps_boxes stay in pre-NMS row order; keep_intermediates adds dets_pre_oks,
     classes_pre_oks, counts_pre_oks and keyps_pre_oks.  Stage mark: misc_oks_nms."""
+    KEYPOINTS = True
+    BOXES_FIRST = True  # _keypoints: the decode's boxes are queued ahead of the head
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
                  det_cap=256, device="cuda", nms_oks=None):
@@ -407,41 +511,55 @@ class KeypointFramePipeline(FramePipeline):
     def _keypoint_heatmaps(self, pyr, krois, klvl, fast):
         """im_detect_keypoints of a padded batch: RoIAlign + head + outputs -> (the
         [rows,K,S,S] logits, the RoI features as NCHW)."""
-        kc = self.cfg.KRCNN
         head = self.model.Keypoint_Head
-        if fast and getattr(head, "nhwc_ready", False):
-            kfeat = ops.roi_align_fpn(pyr, self.roi_scales, krois, klvl, kc.ROI_XFORM_RESOLUTION,
-                                      kc.ROI_XFORM_SAMPLING_RATIO, out_layout="nhwc")
-            x = head.head_nhwc(kfeat)
-            kfeat = kfeat.permute(0, 3, 1, 2)
-        else:
-            kfeat = ops.roi_align_fpn(pyr, self.roi_scales, krois, klvl, kc.ROI_XFORM_RESOLUTION,
-                                      kc.ROI_XFORM_SAMPLING_RATIO)
-            x = head.head(kfeat)
+        x, kfeat = self._roi_head(pyr, krois, klvl, fast, head, self.cfg.KRCNN,
+                                  head.head_nhwc, head.head)
         return self.model.Keypoint_Outs(x).contiguous(), kfeat
 
-    def _keypoint_batch(self, pyr, krois, klvl, kboxes, fast):
-        """RoIAlign + head + outputs + decode of a padded batch (padding rows are zero
-        boxes: a 1 x 1 resized map, never read)."""
-        heat, kfeat = self._keypoint_heatmaps(pyr, krois, klvl, fast)
-        self._mark("im_detect_keypoints")
-        keyps = ops.heatmaps_to_keypoints(heat, kboxes, self.cfg.KRCNN.INFERENCE_MIN_SIZE)
-        self._mark("misc_keypoints")
-        return keyps, heat, kfeat
+    def _stored_boxes(self, src, rows, row0):
+        """Rows [row0, row0 + rows) of src's dets unscaled, the boxes the decode runs
+        against: vd_mask_rois at scale 1 copies the stored boxes bit for bit (a float32
+        times 1.0 in float64), in the batch's row order, zeros past the total."""
+        cfg, dets = self.cfg, src["dets"]
+        return ops.mask_rois(dets, src["classes"], src["counts"], self._ones_d[:dets.shape[0]],
+                             rows, cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL,
+                             row0=row0)[0][:, 1:5]
 
-    def _keypoint_rows(self, out, im_scale_d, rows, row0=0):
-        """Rows [row0, row0 + rows) of the keypoint batch: the scaled RoIs with their
-        levels, and the same rows of dets unscaled -- vd_mask_rois at scale 1 copies
-        the stored boxes bit for bit (a float32 times 1.0 in float64), in the batch's
-        row order, zeros past the total."""
-        cfg = self.cfg
-        dets, dcls, dcnt = out["dets"], out["classes"], out["counts"]
-        krois, klvl, _, ktotal = ops.mask_rois(dets, dcls, dcnt, im_scale_d, rows,
-                                               cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL,
-                                               row0=row0)
-        stored = ops.mask_rois(dets, dcls, dcnt, self._ones_d[:dets.shape[0]], rows,
-                               cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL, row0=row0)[0]
-        return krois, klvl, stored[:, 1:5], ktotal
+    def _decode(self, heats, kboxes, want_combined):
+        """keypoint_results' decode of the head views' heatmaps (here one view's) ->
+        (keyps, the maps that were decoded when want_combined)."""
+        keyps = ops.heatmaps_to_keypoints(heats[0], kboxes, self.cfg.KRCNN.INFERENCE_MIN_SIZE)
+        return keyps, heats[0] if want_combined else None
+
+    def _keypoints(self, out, src, rows, row0=0):
+        """im_detect_keypoints, or im_detect_keypoints_aug, + keypoint_results' decode for
+        rows [row0, row0 + rows) of the keypoint batch of src's detections (padding rows
+        are zero boxes: a 1 x 1 resized map, never read): every head view's heatmaps,
+        then _decode.  -> (keyps, the kps_* tensors of those rows -- rois and features of
+        the identity view, the decoded heatmaps when the step keeps its intermediates
+        -- and the device total).  out["views"], where the step keeps it, is given each
+        view's kps_rois, kps_heatmaps and kps_feat."""
+        keep, views = out["_kps_keep"], out.get("views")
+        # the plain step queues the decode's boxes ahead of the head, the augmented one
+        # behind its views
+        kboxes = self._stored_boxes(src, rows, row0) if self.BOXES_FIRST else None
+        heats, first = [], None
+        for v, (krois, klvl, _, ktotal), pyr, fast in self._view_rois(out, src, rows, row0):
+            heat, kfeat = self._keypoint_heatmaps(pyr, krois, klvl, fast)
+            heats.append(heat)
+            if first is None:
+                first = (krois, kfeat, ktotal)
+            self._keep_view_rows(views, v, row0, kps_rois=krois, kps_heatmaps=heat,
+                                 kps_feat=kfeat)
+        if kboxes is None:
+            kboxes = self._stored_boxes(src, rows, row0)
+        self._mark("im_detect_keypoints")
+        keyps, comb = self._decode(heats, kboxes, keep)
+        self._mark("misc_keypoints")
+        more = {"kps_rois": first[0], "kps_feat": first[1], "kps_boxes": kboxes}
+        if comb is not None:
+            more["kps_heatmaps"] = comb
+        return keyps, more, first[2]
 
     def _oks_nms(self, out, pre, keyps):
         """keypoint_results' OKS NMS of the pre-NMS rows `pre` (dets, classes, counts)
@@ -451,18 +569,15 @@ class KeypointFramePipeline(FramePipeline):
         out.update(dets=res.dets, classes=res.classes, counts=res.counts, keyps=res.keyps,
                    oks_keep=res.keep)
 
-    def _roi_heads(self, out, F, pyr, fast, im_scale_d, keep_intermediates):
-        krois, klvl, kboxes, ktotal = self._keypoint_rows(out, im_scale_d, self.mask_rows(F))
-        keyps, heat, kfeat = self._keypoint_batch(pyr, krois, klvl, kboxes, fast)
-        out["keyps"], out["kps_rois"], out["kps_total"] = keyps, krois, ktotal
+    def _roi_heads(self, out, keep_intermediates):
+        """The keypoint heads and, with nms_oks, the step's OKS NMS of the detections
+        and their raw keypoints."""
         out["_kps_keep"] = keep_intermediates
+        keyps, more, out["kps_total"] = self._keypoints(
+            out, out, self.mask_rows(out["dets"].shape[0]))
+        out["keyps"], out["kps_rois"] = keyps, more["kps_rois"]
         if keep_intermediates:
-            out.update(kps_heatmaps=heat, kps_feat=kfeat, kps_boxes=kboxes)
-        out["_pyr"], out["_fast"], out["_im_scale_d"] = pyr, fast, im_scale_d
-        self._oks_stage(out, keyps, keep_intermediates)
-
-    def _oks_stage(self, out, keyps, keep_intermediates):
-        """With nms_oks: the step's OKS NMS of the detections and their raw keypoints."""
+            out.update(more)
         if self.oks_thresh is not None:
             pre = {k: out[k] for k in ("dets", "classes", "counts", "keyps")}
             out["_oks_pre"] = pre
@@ -470,16 +585,6 @@ class KeypointFramePipeline(FramePipeline):
                 out.update({k + "_pre_oks": v for k, v in pre.items()})
             self._oks_nms(out, pre, keyps)
             self._mark("misc_oks_nms")
-
-    def _raise_on_failed_counts(self, counts):
-        ops.raise_on_failed_counts(counts)
-
-    def _keypoint_overflow(self, out, src, rows, row0):
-        """complete()'s second batch: rows [row0, row0 + rows) of src's detections ->
-        (their keypoints, the kps_* tensors of those rows)."""
-        r2, l2, b2, _ = self._keypoint_rows(src, out["_im_scale_d"], rows, row0=row0)
-        k2, h2, f2 = self._keypoint_batch(out["_pyr"], r2, l2, b2, out["_fast"])
-        return k2, {"kps_rois": r2, "kps_heatmaps": h2, "kps_feat": f2, "kps_boxes": b2}
 
     def complete(self, out: dict) -> dict:
         """FramePipeline.complete for the keypoint outputs: the one host read, the
@@ -498,32 +603,21 @@ class KeypointFramePipeline(FramePipeline):
             F = out["counts"].numel()
             both = torch.cat([pre["counts"], out["counts"]]).cpu().tolist()
             before, counts = both[:F], both[F:]
-        self._raise_on_failed_counts(before)
-        if max(before, default=0) > self.det_cap:
-            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, before))
-        keep = out.pop("_kps_keep", False)
+        self._check_counts(before)
+        keep = out["_kps_keep"]
         keys = ["kps_rois"] + (["kps_heatmaps", "kps_feat", "kps_boxes"] if keep else [])
         raw = out["keyps"] if pre is None else pre["keyps"]  # one row per detection
         M, cap = sum(before), raw.shape[0]
         if M > cap:  # rows [cap, M): a second, rare batch
-            extra = -(-(M - cap) // 64) * 64
-            k2, more = self._keypoint_overflow(out, pre or out, extra, cap)
+            k2, more, _ = self._keypoints(out, pre or out, -(-(M - cap) // 64) * 64, cap)
             for k in keys:
                 out[k] = torch.cat([out[k], more[k]])
             raw = torch.cat([raw, k2])
             if pre is not None:
                 self._oks_nms(out, pre, raw)
                 counts = out["counts"].cpu().tolist()
-        out.pop("_pyr", None)
-        out.pop("_pyrs", None)
-        out.pop("_fast", None)
-        out.pop("_im_scale_d", None)
-        for k in keys:
-            out[k] = out[k][:M]
-        for v in out.get("views", {}).values():  # KeypointAugFramePipeline's per-view rows
-            for k in ("kps_rois", "kps_heatmaps", "kps_feat"):
-                if k in v:
-                    v[k] = v[k][:M]
+        del out["_kps_keep"]
+        self._finish_rows(out, keys, M)
         if pre is None:
             out["keyps"] = raw[:M]
         else:
@@ -555,34 +649,31 @@ def frame_keypoints(pipe: "KeypointFramePipeline", out: dict, num_classes: int =
     return res
 
 
-class _ViewGeom:
-    """Blob geometry of one test-time-augmentation view (scale, max_size, hflip) for
-    frames of one size: FramePipeline's per-frame rows at that view's scale."""
-
-    def __init__(self, view, H, W, stride, F, device):
-        self.view = view
-        self.hflip = bool(view[2])
-        self.scale = ops.target_scale(H, W, view[0], view[1])
-        self.Hr, self.Wr = ops.resized_hw(H, W, self.scale)
-        self.Hp = int(math.ceil(self.Hr / stride) * stride)
-        self.Wp = int(math.ceil(self.Wr / stride) * stride)
-        self.im_info = torch.tensor([[self.Hp, self.Wp, self.scale]] * F, dtype=torch.float32,
-                                    device=device)
-        self.im_scale_t = torch.full((F,), self.scale, dtype=torch.float32, device=device)
-        self.im_scale_d = torch.full((F,), self.scale, dtype=torch.float64, device=device)
-
-
 class _AugViews:
-    """What the test-time-augmentation pipelines share: the views' geometry, their
-    blobs and bodies, and im_detect_bbox_aug's box pass over the box views."""
+    """What the test-time-augmentation pipelines share, mixed in ahead of the plain
+    class: the view table with its budgets, and a box pass that runs im_detect_bbox_aug
+    over the box views (box_union) and the bodies of the remaining head views."""
 
-    def _make_geoms(self, views, batch):
-        self.geom = {}
-        for v in views:
+    def _setup_views(self, box_views, head_views, cand_cap, pyramid_budget_bytes, kind, key):
+        """geom[view] for every distinct view, the union's capacity, and the budget of
+        the pyramids kept for the heads (kind, key: the head views' name in its error)."""
+        cfg, batch = self.cfg, self.F
+        self.box_views, self.head_views = box_views, head_views
+        self.geom = {self.ident.view: self.ident}
+        for v in box_views + head_views:
             if v not in self.geom:
-                self.geom[v] = _ViewGeom(v, self.H, self.W, self.cfg.FPN.COARSEST_STRIDE, batch,
+                self.geom[v] = _ViewGeom(v, self.H, self.W, cfg.FPN.COARSEST_STRIDE, batch,
                                          self.device)
         self._unions = {}
+        post = int(cfg.TEST.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
+        self.cand_cap = int(cand_cap or min(ops.UNION_MAX_CAND, len(box_views) * post))
+        kept = sum(self.pyramid_bytes(self.geom[v]) for v in set(head_views))
+        if batch * kept > pyramid_budget_bytes:
+            raise ValueError(
+                "%s: the %d %s views' pyramids take %d x %d bytes, over pyramid_budget_bytes "
+                "= %d (fewer frames per step, or fewer %s views)"
+                % (type(self).__name__, len(set(head_views)), kind, batch, kept,
+                   pyramid_budget_bytes, key))
 
     def pyramid_bytes(self, g) -> int:
         """Bytes of one frame's RoI pyramid (P2..P5, FPN.DIM channels, fp32) at view g."""
@@ -591,48 +682,60 @@ class _AugViews:
             n += -(-g.Hp // 2 ** lvl) * -(-g.Wp // 2 ** lvl)
         return n * int(self.cfg.FPN.DIM) * 4
 
-    def _view_blob(self, frames, g):
-        """make_blob at view g's geometry."""
-        nhwc = self.channels_last
-        if g.scale == 1.0:
-            blob = ops.image_to_blob(frames, self.lut, g.Hp, g.Wp, nhwc=nhwc)
-        else:
-            blob = ops.image_resize_to_blob(frames, self.lut, g.scale, g.Hp, g.Wp, nhwc=nhwc)
-        return blob.permute(0, 3, 1, 2) if nhwc else blob
-
     def _union(self, F, K):
         if (F, K) not in self._unions:
             self._unions[(F, K)] = ops.BoxUnion(self.cand_cap, F, K, self.device)
         return self._unions[(F, K)]
 
-    def _flipped_frames(self, frames):
-        return frames.flip(2) if any(v[2] for v in self.geom) else None
+    def _view_body(self, frames, flipped, g):
+        """View g's blob, of the frames or their horizontal flip, and its body."""
+        blob = self.make_blob(flipped if g.hflip else frames, g)
+        return blob, self.model.Conv_Body(blob)
 
-    def _box_pass(self, frames, flipped, head_views, keep_intermediates):
+    def _box_pass(self, frames, keep_intermediates=False):
+        """The box pass over the box views (box_union) or the plain one, then the bodies
+        of the head views it did not run (the reference's im_conv_body_only).  A head
+        view keeps its pyramid for the head pass; keep_intermediates adds out["views"]."""
+        F = frames.shape[0]
+        flipped = frames.flip(2) if any(v[2] for v in self.geom) else None
+        views = {}
+        if self.box_union:
+            out = self._union_pass(frames, flipped, views, keep_intermediates)
+        else:
+            out = super()._box_pass(frames, keep_intermediates)
+        pyrs = out["_pyrs"]
+        for v in self.head_views:
+            if v not in pyrs:
+                g = self.geom[v].rows(F)
+                blob, feats = self._view_body(frames, flipped, g)
+                pyrs[v] = (g, self.nhwc_pyramid(feats), self._nhwc_heads())
+                self._mark("conv_body")
+                if keep_intermediates:
+                    views.setdefault(v, {}).update(pyramid=pyrs[v][1], blob=blob)
+        if keep_intermediates:
+            out["views"] = views
+        return out
+
+    def _union_pass(self, frames, flipped, views, keep_intermediates):
         """im_detect_bbox_aug + box_results_with_nms_and_limit: every box view's body and
-        box stages folded into the union, then the detections.  A view of head_views
-        keeps its pyramid for the head pass.  -> (out, pyrs, views)."""
+        box stages folded into the union, then the detections."""
         cfg, tst = self.cfg, self.cfg.TEST
         F = frames.shape[0]
-        im_hw = self.im_hw[:F]
-        head_set = set(head_views)
-        pyrs, views, union = {}, {}, None
+        pyrs, union = {}, None
         for i, v in enumerate(self.box_views):
-            g = self.geom[v]
-            blob = self._view_blob(flipped if g.hflip else frames, g)
-            feats = self.model.Conv_Body(blob)
+            g = self.geom[v].rows(F)
+            blob, feats = self._view_body(frames, flipped, g)
             self._mark("conv_body")
             rois, rcnt, cls_prob, bbox_pred, _, _, pyr, fast, post = \
-                self._box_stages(feats, g.im_info[:F])
+                self._box_stages(feats, g.im_info)
             K = cls_prob.shape[1]
-            bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, K)
             union = union or self._union(F, K)
             union.add_view(rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
-                           g.im_scale_t[:F], im_hw, g.hflip, tst.SCORE_THRESH,
+                           g.im_scale_t, g.im_hw, g.hflip, tst.SCORE_THRESH,
                            cfg.MODEL.BBOX_REG_WEIGHTS, first=i == 0)
             self._mark("union_add_view")
-            if v in head_set:
-                pyrs[v] = (pyr, fast)
+            if v in self.head_views:
+                pyrs[v] = (g, pyr, fast)
             if keep_intermediates:
                 views[v] = dict(rois=rois, roi_counts=rcnt, cls_prob=cls_prob,
                                 bbox_pred=bbox_pred, pyramid=pyr, blob=blob)
@@ -642,33 +745,10 @@ class _AugViews:
             num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE, cand_counts=cand,
             **self._nms_options)
         self._mark("misc_bbox")
-        ident = views.get(self.box_views[-1]) or dict(rois=rois, roi_counts=rcnt,
-                                                      cls_prob=cls_prob, bbox_pred=bbox_pred)
-        out = {"dets": dets, "classes": dcls, "counts": dcnt, "cand_counts": cand,
-               "rois": ident["rois"], "roi_counts": ident["roi_counts"],
-               "cls_prob": ident["cls_prob"], "bbox_pred": ident["bbox_pred"]}
-        return out, pyrs, views
-
-    def _body_only(self, frames, flipped, head_views, pyrs, views, keep_intermediates):
-        """The bodies of the head views the box pass did not run (the reference's
-        im_conv_body_only), added to pyrs."""
-        for v in head_views:
-            if v not in pyrs:
-                g = self.geom[v]
-                blob = self._view_blob(flipped if g.hflip else frames, g)
-                pyrs[v] = (self.nhwc_pyramid(self.model.Conv_Body(blob)),
-                           self.channels_last and getattr(self.model.Box_Head, "nhwc_ready",
-                                                          False))
-                self._mark("conv_body")
-                if keep_intermediates:
-                    views.setdefault(v, {}).update(pyramid=pyrs[v][0], blob=blob)
-
-    def _hflip_dets(self, dets):
-        """flip_boxes of the detections, float32: x1' = (W - x2) - 1."""
-        dets_hf = dets.clone()
-        dets_hf[..., 0] = self.W - dets[..., 2] - 1
-        dets_hf[..., 2] = self.W - dets[..., 0] - 1
-        return dets_hf
+        # the identity view is the last box view: its rows are the step's
+        return {"dets": dets, "classes": dcls, "counts": dcnt, "cand_counts": cand,
+                "rois": rois, "roi_counts": rcnt, "cls_prob": cls_prob, "bbox_pred": bbox_pred,
+                "_pyrs": pyrs}
 
     def _raise_on_failed_union(self, counts):
         if any(c < 0 for c in counts):
@@ -703,6 +783,9 @@ class AugFramePipeline(_AugViews, FramePipeline):
     view a dict with rois, roi_counts, cls_prob, bbox_pred, pyramid and blob (box views)
     and mask_rois, masks (mask views), and out["cand_counts"] [F,K]."""
 
+    TEST_AUG = ("BBOX_AUG", "MASK_AUG")
+    box_union = True  # one box view too goes through the union
+
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
                  det_cap=256, device="cuda", cand_cap=None, pyramid_budget_bytes=24 << 30):
         from . import config as vcfg
@@ -713,89 +796,13 @@ class AugFramePipeline(_AugViews, FramePipeline):
                 "KeypointAugFramePipeline)")
         vcfg.check_supported(cfg, test_aug=True)
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
-        self.box_views, self.mask_views = vcfg.aug_views(cfg)
-        self._make_geoms(self.box_views + self.mask_views, batch)
+        box_views, self.mask_views = vcfg.aug_views(cfg)
         self.mask_heur = cfg.TEST.MASK_AUG.HEUR if cfg.TEST.MASK_AUG.ENABLED else "SOFT_AVG"
-        post = int(cfg.TEST.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
-        self.cand_cap = int(cand_cap or min(ops.UNION_MAX_CAND, len(self.box_views) * post))
-        kept = sum(self.pyramid_bytes(self.geom[v]) for v in set(self.mask_views))
-        if batch * kept > pyramid_budget_bytes:
-            raise ValueError(
-                "AugFramePipeline: the %d mask views' pyramids take %d x %d bytes, over "
-                "pyramid_budget_bytes = %d (fewer frames per step, or fewer MASK_AUG views)"
-                % (len(set(self.mask_views)), batch, kept, pyramid_budget_bytes))
+        self._setup_views(box_views, self.mask_views, cand_cap, pyramid_budget_bytes,
+                          "mask", "MASK_AUG")
 
-    def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
-        F = frames.shape[0]
-        flipped = self._flipped_frames(frames)
-        out, pyrs, views = self._box_pass(frames, flipped, self.mask_views, keep_intermediates)
-        self._body_only(frames, flipped, self.mask_views, pyrs, views, keep_intermediates)
-        if keep_intermediates:
-            out["views"] = views
-        out["_pyrs"] = pyrs
-        out["masks"], out["mask_rois"], out["mask_feat"], out["mask_total"] = \
-            self._aug_masks(out, self.mask_rows(F), 0, views if keep_intermediates else None)
-        self._mark("im_detect_mask")
-        if sync:
-            self.complete(out)
-        return out
-
-    def _aug_masks(self, out, rows, row0, views=None):
-        """im_detect_mask_aug for rows [row0, row0 + rows) of the mask batch: every mask
-        view's masks combined by TEST.MASK_AUG.HEUR.  -> (masks, the identity view's
-        mask_rois and mask_feat, the device total)."""
-        cfg = self.cfg
-        dets, dcls, dcnt = out["dets"], out["classes"], out["counts"]
-        F = dets.shape[0]
-        dets_hf = None
-        acc = first = None
-        for i, v in enumerate(self.mask_views):
-            g = self.geom[v]
-            d = dets
-            if g.hflip:
-                if dets_hf is None:
-                    dets_hf = self._hflip_dets(dets)
-                d = dets_hf
-            mrois, mlvl, mcls, mtotal = ops.mask_rois(
-                d, dcls, dcnt, g.im_scale_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
-                cfg.FPN.ROI_MAX_LEVEL, row0=row0)
-            pyr, fast = out["_pyrs"][v]
-            masks, mfeat = self._mask_batch(pyr, mrois, mlvl, mcls, fast)
-            masks = masks.contiguous()
-            if i == 0:
-                acc = torch.empty_like(masks)
-                first = (mrois, mfeat, mtotal)
-            ops.mask_aug_accumulate(acc, masks, g.hflip, self.mask_heur, first=i == 0)
-            if views is not None:
-                views.setdefault(v, {}).update(mask_rois=mrois, masks=masks)
-        ops.mask_aug_finish(acc, len(self.mask_views), self.mask_heur)
-        return acc, first[0], first[1], first[2]
-
-    def complete(self, out: dict) -> dict:
-        """FramePipeline.complete; the rare rows past the padded mask batch run through
-        every mask view again."""
-        if "counts_host" in out:
-            return out
-        counts = out["counts"].cpu().tolist()
+    def _raise_on_failed_counts(self, counts):
         self._raise_on_failed_union(counts)
-        if max(counts, default=0) > self.det_cap:
-            raise RuntimeError("detections exceed det_cap=%d: %s" % (self.det_cap, counts))
-        M, cap = sum(counts), out["masks"].shape[0]
-        if M > cap:
-            extra = -(-(M - cap) // 64) * 64
-            m2, r2, f2, _ = self._aug_masks(out, extra, cap)
-            out["masks"] = torch.cat([out["masks"], m2])
-            out["mask_feat"] = torch.cat([out["mask_feat"], f2])
-            out["mask_rois"] = torch.cat([out["mask_rois"], r2])
-        out.pop("_pyrs", None)
-        for k in ("masks", "mask_feat", "mask_rois"):
-            out[k] = out[k][:M]
-        for v in out.get("views", {}).values():
-            for k in ("mask_rois", "masks"):
-                if k in v:
-                    v[k] = v[k][:M]
-        out["counts_host"] = counts
-        return out
 
 
 class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
@@ -824,6 +831,9 @@ class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
     the identity view's.  Stage marks: conv_body, union_add_view, misc_bbox,
     im_detect_keypoints, misc_keypoints, misc_oks_nms."""
 
+    TEST_AUG = ("BBOX_AUG", "KPS_AUG")
+    BOXES_FIRST = False
+
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
                  det_cap=256, device="cuda", nms_oks=None, cand_cap=None,
                  pyramid_budget_bytes=24 << 30, heatmap_budget_bytes=8 << 30):
@@ -831,8 +841,7 @@ class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
         vcfg.check_supported(cfg, test_aug=True)
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device, nms_oks)
         tst = cfg.TEST
-        self.bbox_aug = bool(tst.BBOX_AUG.ENABLED)
-        self.box_views = vcfg.aug_views(cfg)[0]
+        self.bbox_aug = self.box_union = bool(tst.BBOX_AUG.ENABLED)
         self.kps_views, self.kps_ds, self.kps_us = vcfg.kps_aug_views(cfg)
         if len(set(self.kps_views)) != len(self.kps_views):
             raise ValueError("KeypointAugFramePipeline: TEST.KPS_AUG lists a view twice: %s"
@@ -840,18 +849,11 @@ class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
         if len(self.kps_views) > ops.KPS_AUG_MAX_VIEWS:
             raise ValueError("KeypointAugFramePipeline: %d keypoint views, the combination "
                              "takes %d" % (len(self.kps_views), ops.KPS_AUG_MAX_VIEWS))
-        self._make_geoms(self.box_views + self.kps_views, batch)
         self.kps_heur = tst.KPS_AUG.HEUR if tst.KPS_AUG.ENABLED else "HM_AVG"
         self.kps_area_th = float(tst.KPS_AUG.AREA_TH) \
             if tst.KPS_AUG.ENABLED and tst.KPS_AUG.SCALE_SIZE_DEP else None
-        post = int(tst.RPN_POST_NMS_TOP_N * cfg.FPN.RPN_COLLECT_SCALE + 0.5)
-        self.cand_cap = int(cand_cap or min(ops.UNION_MAX_CAND, len(self.box_views) * post))
-        kept = sum(self.pyramid_bytes(self.geom[v]) for v in self.kps_views)
-        if batch * kept > pyramid_budget_bytes:
-            raise ValueError(
-                "KeypointAugFramePipeline: the %d keypoint views' pyramids take %d x %d bytes, "
-                "over pyramid_budget_bytes = %d (fewer frames per step, or fewer KPS_AUG views)"
-                % (len(self.kps_views), batch, kept, pyramid_budget_bytes))
+        self._setup_views(vcfg.aug_views(cfg)[0], self.kps_views, cand_cap,
+                          pyramid_budget_bytes, "keypoint", "KPS_AUG")
         V, rows = len(self.kps_views), self.mask_rows(batch)
         K, S = int(cfg.KRCNN.NUM_KEYPOINTS), int(cfg.KRCNN.HEATMAP_SIZE)
         if V * rows * K * S * S * 4 > heatmap_budget_bytes:
@@ -862,83 +864,13 @@ class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
                 % (V, rows, K, S, S, K * S * S * 4, V * rows * K * S * S * 4,
                    heatmap_budget_bytes))
 
-    def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
-        F = frames.shape[0]
-        flipped = self._flipped_frames(frames)
-        ident = self.kps_views[0]
-        if self.bbox_aug:
-            out, pyrs, views = self._box_pass(frames, flipped, self.kps_views,
-                                              keep_intermediates)
-        else:
-            out, F, pyr, fast, _ = self._detect(frames, keep_intermediates)
-            pyrs, views = {ident: (pyr, fast)}, {}
-        self._body_only(frames, flipped, self.kps_views, pyrs, views, keep_intermediates)
-        if keep_intermediates:
-            out["views"] = views
-        out["_pyrs"] = pyrs
-        out["_kps_keep"] = keep_intermediates
-        keyps, more, out["kps_total"] = self._aug_keypoints(
-            out, out, self.mask_rows(F), 0, views if keep_intermediates else None)
-        out["keyps"], out["kps_rois"] = keyps, more["kps_rois"]
-        if keep_intermediates:
-            out.update(more)
-        self._oks_stage(out, keyps, keep_intermediates)
-        if sync:
-            self.complete(out)
-        return out
-
-    def _aug_keypoints(self, out, src, rows, row0, views=None):
-        """im_detect_keypoints_aug + keypoint_results' decode for rows [row0, row0 + rows)
-        of the keypoint batch of src's detections: every view's heatmaps, then one
-        combine-and-decode launch.  -> (keyps, the kps_* tensors of those rows -- rois
-        and features of the identity view, the combined heatmaps when views is given --
-        and the device total).  views: the keep_intermediates dict, given each view's
-        kps_rois, kps_heatmaps and kps_feat (appended to rows already there)."""
-        cfg = self.cfg
-        dets, dcls, dcnt = src["dets"], src["classes"], src["counts"]
-        F = dets.shape[0]
-        dets_hf = None
-        heats, first = [], None
-        for i, v in enumerate(self.kps_views):
-            g = self.geom[v]
-            d = dets
-            if g.hflip:
-                if dets_hf is None:
-                    dets_hf = self._hflip_dets(dets)
-                d = dets_hf
-            krois, klvl, _, ktotal = ops.mask_rois(
-                d, dcls, dcnt, g.im_scale_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
-                cfg.FPN.ROI_MAX_LEVEL, row0=row0)
-            pyr, fast = out["_pyrs"][v]
-            heat, kfeat = self._keypoint_heatmaps(pyr, krois, klvl, fast)
-            heats.append(heat)
-            if i == 0:
-                first = (krois, kfeat, ktotal)
-            if views is not None:
-                new = dict(kps_rois=krois, kps_heatmaps=heat, kps_feat=kfeat)
-                vd = views.setdefault(v, {})
-                for k, t in new.items():
-                    vd[k] = torch.cat([vd[k], t]) if row0 and k in vd else t
-        # the decode's boxes: the stored detections of the same rows (_keypoint_rows)
-        kboxes = ops.mask_rois(dets, dcls, dcnt, self._ones_d[:F], rows, cfg.FPN.ROI_MIN_LEVEL,
-                               cfg.FPN.ROI_MAX_LEVEL, row0=row0)[0][:, 1:5]
-        self._mark("im_detect_keypoints")
+    def _decode(self, heats, kboxes, want_combined):
+        """One launch combines the views' heatmaps and decodes them (also with one view)."""
         res = ops.heatmaps_to_keypoints_aug(
             heats, [self.geom[v].hflip for v in self.kps_views], self.kps_ds, self.kps_us,
-            kboxes, cfg.KRCNN.INFERENCE_MIN_SIZE, self.kps_heur, self.kps_area_th,
-            want_combined=views is not None)
-        self._mark("misc_keypoints")
-        keyps, comb = res if views is not None else (res, None)
-        more = {"kps_rois": first[0], "kps_feat": first[1], "kps_boxes": kboxes}
-        if comb is not None:
-            more["kps_heatmaps"] = comb
-        return keyps, more, first[2]
-
-    def _keypoint_overflow(self, out, src, rows, row0):
-        """complete()'s rare rows past the padded batch run through every keypoint view
-        again (out["views"] is there exactly when the step kept its intermediates)."""
-        keyps, more, _ = self._aug_keypoints(out, src, rows, row0, out.get("views"))
-        return keyps, more
+            kboxes, self.cfg.KRCNN.INFERENCE_MIN_SIZE, self.kps_heur, self.kps_area_th,
+            want_combined=want_combined)
+        return res if want_combined else (res, None)
 
     def _raise_on_failed_counts(self, counts):
         if self.bbox_aug:
@@ -1060,7 +992,7 @@ class RaggedFramePipeline(FramePipeline):
         return blob.permute(0, 3, 1, 2) if nhwc else blob  # NCHW view
 
     def _frame_rows(self, batch: RaggedBatch):
-        return batch.F, batch.im_info, batch.im_scale_t, batch.im_scale_d, batch.im_hw
+        return batch  # it carries the per-frame rows itself
 
     @torch.no_grad()
     def run(self, batch: RaggedBatch, keep_intermediates: bool = False, sync: bool = True):
