@@ -4,8 +4,10 @@ vd_fpn_lateral_topdown) vs the reference's PyTorch sequence in fp32
 scale_factor=2, mode='nearest')): within 2e-5 of the output range (the GEMM's
 summation order differs from the library conv's; the bias and the top-down term
 are added in the reference's order).  Small shapes with ragged tiles (M not a
-multiple of the 128 / 256-pixel tile), every K the kernel serves, the no-top form,
-the benched P2-P4 shapes (256-pixel tiles), and graph capture."""
+multiple of the 64-pixel tile), every K the kernel serves, the no-top form, the
+benched P2-P4 shapes, and graph capture.  Every launch here takes the 64-pixel
+(NB = 1) form; the 128-pixel form needs CUs x 1024 rows without a top-down map and
+runs in tests/test_gemm_exact_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

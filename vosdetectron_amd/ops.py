@@ -1093,12 +1093,13 @@ def fpn_lateral_weight(w: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def fpn_lateral_topdown(lateral: torch.Tensor, wf: torch.Tensor, bias: torch.Tensor,
-                        top: Optional[torch.Tensor]) -> torch.Tensor:
+                        top: Optional[torch.Tensor],
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """FPN.py topdown_lateral_module.forward (:292-300) in one MFMA launch
     (vd_fpn_lateral_topdown): conv_lateral(lateral) + nearest-2x(top), the sum in the
     reference's order ((conv + bias) + top).  lateral: channels_last N x K x H x W fp32;
     top: channels_last N x 256 x H/2 x W/2 (None: the lateral conv alone); wf from
-    fpn_lateral_weight.  Returns a channels_last N x 256 x H x W tensor."""
+    fpn_lateral_weight.  Returns a channels_last N x 256 x H x W tensor (`out` when given)."""
     if not lateral.is_cuda or lateral.dtype != torch.float32 or lateral.dim() != 4 \
             or not lateral.is_contiguous(memory_format=torch.channels_last):
         raise ValueError("lateral must be a channels_last fp32 device tensor")
@@ -1118,8 +1119,12 @@ def fpn_lateral_topdown(lateral: torch.Tensor, wf: torch.Tensor, bias: torch.Ten
         # (not _need: its .contiguous() would copy a channels_last tensor to NCHW)
         t_ = top if top.is_contiguous(memory_format=torch.channels_last) else \
             top.contiguous(memory_format=torch.channels_last)
-    out = torch.empty((N, 256, H, W), dtype=torch.float32, device=lateral.device,
-                      memory_format=torch.channels_last)
+    if out is None:
+        out = torch.empty((N, 256, H, W), dtype=torch.float32, device=lateral.device,
+                          memory_format=torch.channels_last)
+    elif tuple(out.shape) != (N, 256, H, W) or out.dtype != torch.float32 or not out.is_cuda \
+            or not out.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("out must be a channels_last fp32 %s device tensor" % ((N, 256, H, W),))
     check(lib().vd_fpn_lateral_topdown(lateral.data_ptr(), N * H * W, K, wf_.data_ptr(), 256,
                                        b_.data_ptr(), t_.data_ptr() if t_ is not None else None,
                                        H, W, out.data_ptr(), _stream()),
