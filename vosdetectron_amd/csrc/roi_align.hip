@@ -569,8 +569,14 @@ __device__ __forceinline__ void pipe_row(const RoiGeom &g, ra_v4i desc, int voff
             consume(k + 1, s1);
         }
     }
+    // No load outlives the row's slots: the loads of a padding column (one past the list,
+    // or all of them when no sample of the row is in range) are never combined, so their
+    // slots are dead from the issue on and only this wait retires them.  It stands before
+    // the last finish(): after it, that finish()'s store data was built in a slot's
+    // registers while the load was still in flight, and a RoI wholly off the map stored
+    // pixel (0, 0) instead of 0 whenever the load was slow.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     finish(0x7fffffff);  // samples past the last column: all invalid; their bins store 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no load outlives the row's slots
 }
 
 template <bool NT, int D>
