@@ -585,6 +585,29 @@ int vd_image_resize_to_blob(const uint8_t *frames, int F, int H, int W, const fl
                             double im_scale, int Hr, int Wr, int Hp, int Wp, int nhwc,
                             float *blob, void *stream);
 
+/* The blob of an aspect-ratio view of the test-time augmentation (lib/core/test.py:
+ * 330-363, 509-526, 684-702) in one launch:
+ *   im_ar = cv2.resize(im, dsize=(War, H)), War = int(round(ar * W))
+ *           (lib/utils/image.py:27-32: u8 -> u8 INTER_LINEAR of the width alone),
+ *   the network sees im_ar[:, ::-1] when hflip != 0,
+ *   then vd_image_resize_to_blob's steps on that H x War image at im_scale
+ *   (Hr x Wr = rint(H * im_scale), rint(War * im_scale); the 2 x 2 area path at
+ *   im_scale == 0.5), zero-padded to Hp x Wp.
+ * im_ar is never written: each of its pixels that the float resize taps is made
+ * from two horizontally adjacent bytes of the frame by OpenCV's 8-bit fixed-point
+ * path (scale = 1 / ((double)War / W); fx = (float)((dx + 0.5) * scale - 0.5), sx =
+ * floor(fx), fx -= sx, clamped as the float path clamps; a0 = rint((1.f - fx) * 2048),
+ * a1 = rint(fx * 2048), each rounded half to even on its own; D = S[sx] * a0 +
+ * S[sx + 1] * a1 in int32; out = (uint8)(((D >> 9) + 2) >> 2), the vertical pass with
+ * coefficients (2048, 0)).  The flip is applied to im_ar, after the 8-bit resize, as
+ * the reference does: pass the unflipped frames.  Every blob element is written; all
+ * source indices are clamped to the frame.  cv2 is not importable in the build
+ * container, so parity of the 8-bit step against an executed cv2 is unpinned, as the
+ * float step's is (both are pinned against the numpy restatement and known answers). */
+int vd_image_aspect_resize_to_blob(const uint8_t *frames, int F, int H, int W, int War, int hflip,
+                                   const float *lut, double im_scale, int Hr, int Wr, int Hp,
+                                   int Wp, int nhwc, float *blob, void *stream);
+
 /* Frames of different sizes in one launch: im_list_to_blob (lib/utils/blob.py:
  * 86-114) over per-frame prep_im_for_blob results, as tools/infer_simple.py and
  * test_net.py meet them.  Frame f is geom[f].H x geom[f].W x 3 u8 BGR starting
@@ -965,6 +988,13 @@ int vd_compute_oks(const float *src_keypoints, const float *src_roi, const float
  * 1), and appended in row order behind the earlier views' rows.  A list that would
  * exceed cand_cap, or a negative roi_count, fails the image.
  *
+ * vd_box_union_add_view_ar: the same for an aspect-ratio view (test.py:330-363).
+ * im_hw[i] = (H, War), the view's im_ar: the clip and the flip-back use it.  After
+ * them x1' = fl32(x1 * x_inv), x2' = fl32(x2 * x_inv): aspect_ratio(boxes, 1.0 / ar)
+ * (lib/utils/boxes.py:269-274), x_inv = float32(1.0 / ar) with the division in double
+ * (numpy multiplies a float32 array by a Python float in float32).  x_inv must be
+ * positive and finite.
+ *
  * vd_box_union_detections: per (image, class) the list sorted by (score
  * descending, higher vstack index first), greedy NMS at any length without an
  * n x n mask, TEST.SOFT_NMS / TEST.BBOX_VOTE as vd_box_detections_ex (voters: all
@@ -979,6 +1009,11 @@ int vd_box_union_add_view(const float *rois, const float *cls_prob, const float 
                           const float *im_scale, const int32_t *im_hw, int hflip, int first,
                           float score_thresh, const float *bbox_reg_weights, int cand_cap,
                           void *workspace, size_t workspace_bytes, void *stream);
+int vd_box_union_add_view_ar(const float *rois, const float *cls_prob, const float *bbox_pred,
+                             const int32_t *roi_count, int R_cap, int num_images, int num_classes,
+                             const float *im_scale, const int32_t *im_hw, int hflip, float x_inv,
+                             int first, float score_thresh, const float *bbox_reg_weights,
+                             int cand_cap, void *workspace, size_t workspace_bytes, void *stream);
 int vd_box_union_detections(int cand_cap, int num_images, int num_classes, float nms_thresh,
                             int dets_per_im, int soft_nms_method, float soft_nms_sigma,
                             float soft_nms_min_score, int bbox_vote_method,

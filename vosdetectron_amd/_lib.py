@@ -119,6 +119,8 @@ SIGNATURES = {
     "vd_box_union_workspace_size": (_S, [_I, _I, _I]),
     "vd_box_union_add_view": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _F, _P, _I, _P,
                                    _S, _P]),
+    "vd_box_union_add_view_ar": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _F, _I, _F, _P, _I,
+                                      _P, _S, _P]),
     "vd_box_union_detections": (_I, [_I, _I, _I, _F, _I, _I, _F, _F, _I, _F, _F, _I, _P, _P, _P,
                                      _P, _P, _S, _P]),
     "vd_mask_aug_accumulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
@@ -134,6 +136,8 @@ SIGNATURES = {
     "vd_image_to_blob": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "vd_image_resize_to_blob": (_I, [_P, _I, _I, _I, _P, ctypes.c_double, _I, _I, _I, _I, _I,
                                      _P, _P]),
+    "vd_image_aspect_resize_to_blob": (_I, [_P, _I, _I, _I, _I, _I, _P, ctypes.c_double, _I, _I,
+                                            _I, _I, _I, _P, _P]),
     "vd_image_resize_to_blob_ragged": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "vd_nchw_to_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "vd_bias_act": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

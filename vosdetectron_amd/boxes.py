@@ -49,6 +49,18 @@ def flip_boxes(boxes, im_width):
     return flipped
 
 
+def aspect_ratio(boxes, aspect_ratio):
+    """Perform width-relative aspect ratio transformation (lib/utils/boxes.py:269-274):
+    x1, x2 of an (N, 4k) ndarray, or a tensor on any device, times aspect_ratio.  The
+    product stays in the boxes' dtype: float32 boxes are multiplied by
+    float32(aspect_ratio), what numpy computes for a float32 array times a Python float
+    and what the union's aspect-ratio views compute on the device."""
+    boxes_ar = boxes.clone() if isinstance(boxes, torch.Tensor) else boxes.copy()
+    boxes_ar[:, 0::4] = aspect_ratio * boxes[:, 0::4]
+    boxes_ar[:, 2::4] = aspect_ratio * boxes[:, 2::4]
+    return boxes_ar
+
+
 def _dev(d):
     return torch.from_numpy(np.ascontiguousarray(d, np.float32)).to(
         torch.device("cuda", torch.cuda.current_device()))

@@ -223,9 +223,11 @@ def _float32_exact(v):
 UNSUPPORTED_TEST_AUG = tuple(
     (key, _WithCfg(pred), where) for key, pred, where in (
         ("TEST.BBOX_AUG.ASPECT_RATIOS", _aug_on("BBOX_AUG"),
-         "aspect-ratio views need an anisotropic resize, lib/core/test.py:330-363"),
+         "aspect-ratio views need an anisotropic resize, lib/core/test.py:330-363; "
+         "load_cfg(..., test_aug=True, aspect_views=True) accepts them"),
         ("TEST.MASK_AUG.ASPECT_RATIOS", _aug_on("MASK_AUG"),
-         "aspect-ratio views need an anisotropic resize, lib/core/test.py:509-526"),
+         "aspect-ratio views need an anisotropic resize, lib/core/test.py:509-526; "
+         "load_cfg(..., test_aug=True, aspect_views=True) accepts them"),
         ("TEST.BBOX_AUG.SCALE_SIZE_DEP", _aug_on("BBOX_AUG"),
          "the reference asserts it off, lib/core/test.py:197"),
         ("TEST.MASK_AUG.SCALE_SIZE_DEP", _aug_on("MASK_AUG"),
@@ -241,7 +243,8 @@ UNSUPPORTED_TEST_AUG = tuple(
         ("TEST.MASK_AUG.ENABLED", lambda v, c: bool(v) and bool(c.MODEL.KEYPOINTS_ON),
          "a MODEL.KEYPOINTS_ON model has no mask head"),
         ("TEST.KPS_AUG.ASPECT_RATIOS", _aug_on("KPS_AUG"),
-         "aspect-ratio views need an anisotropic resize, lib/core/test.py:684-702"),
+         "aspect-ratio views need an anisotropic resize, lib/core/test.py:684-702; "
+         "load_cfg(..., test_aug=True, aspect_views=True) accepts them"),
         ("TEST.KPS_AUG.HEUR", _aug_not("KPS_AUG", KPS_AUG_HEURS),
          "the reference raises, lib/core/test.py:631-638"),
         ("TEST.KPS_AUG.AREA_TH", lambda v, c: bool(c.TEST.KPS_AUG.ENABLED) and bool(
@@ -251,15 +254,50 @@ UNSUPPORTED_TEST_AUG = tuple(
     ))
 
 
-def check_supported(cfg, test_aug: bool = False) -> None:
+# The keys of UNSUPPORTED_TEST_AUG that aspect_views=True accepts (the views run on the
+# augmented pipelines through vd_image_aspect_resize_to_blob).
+ASPECT_VIEW_KEYS = ("TEST.BBOX_AUG.ASPECT_RATIOS", "TEST.MASK_AUG.ASPECT_RATIOS",
+                    "TEST.KPS_AUG.ASPECT_RATIOS")
+
+
+def aspect_width(im_w: int, ar: float) -> int:
+    """aspect_ratio_rel's width (lib/utils/image.py:30): int(round(ar * im_w))."""
+    return int(round(float(ar) * im_w))
+
+
+def check_aspect_ratios(cfg, im_w=None) -> None:
+    """Raise ValueError for an enabled ASPECT_RATIOS entry that is not a positive finite
+    number or, given the frame width im_w, whose view would be under 2 columns wide."""
+    bad = []
+    for key in ASPECT_VIEW_KEYS:
+        aug = cfg.TEST[key.split(".")[1]]
+        if not aug.ENABLED:
+            continue
+        for ar in aug.ASPECT_RATIOS:
+            try:
+                f = float(ar)
+            except (TypeError, ValueError):
+                f = float("nan")
+            if isinstance(ar, bool) or not (f > 0.0 and math.isfinite(f)):
+                bad.append("%s holds %r: a ratio is a positive finite number" % (key, ar))
+            elif im_w is not None and aspect_width(im_w, f) < 2:
+                bad.append("%s holds %r: at frame width %d the view is %d column(s) wide, "
+                           "under 2" % (key, ar, im_w, aspect_width(im_w, f)))
+    if bad:
+        raise ValueError("aspect-ratio views: " + "; ".join(bad))
+
+
+def check_supported(cfg, test_aug: bool = False, aspect_views: bool = False) -> None:
     """Raise NotImplementedError naming every enabled option of ``UNSUPPORTED``;
     test_aug accepts TEST.BBOX_AUG / TEST.MASK_AUG / TEST.KPS_AUG but for
-    ``UNSUPPORTED_TEST_AUG``."""
+    ``UNSUPPORTED_TEST_AUG``; aspect_views (with test_aug) also accepts the three
+    ``ASPECT_VIEW_KEYS`` and checks their ratios (check_aspect_ratios: ValueError)."""
     bad = []
     table = UNSUPPORTED
     if test_aug:
         table = tuple(r for r in UNSUPPORTED if r[0] not in TEST_AUG_KEYS + (KPS_AUG_KEY,)) \
-            + UNSUPPORTED_TEST_AUG
+            + tuple(r for r in UNSUPPORTED_TEST_AUG
+                    if not (aspect_views and r[0] in ASPECT_VIEW_KEYS))
     for key, enabled, where in table:
         try:
             v = _get(cfg, key)
@@ -270,15 +308,20 @@ def check_supported(cfg, test_aug: bool = False) -> None:
     if bad:
         raise NotImplementedError("inference options not implemented by vosdetectron_amd: "
                                   + "; ".join(bad))
+    if test_aug and aspect_views:
+        check_aspect_ratios(cfg)
 
 
 def aug_views(cfg):
     """The views of im_detect_bbox_aug / im_detect_mask_aug as two ordered lists of
     (scale, max_size, hflip).  Box views in np.vstack order (lib/core/test.py:218-261):
     the flipped view at (TEST.SCALE, TEST.MAX_SIZE), each BBOX_AUG.SCALES entry (then
-    its flip with SCALE_H_FLIP), the identity view LAST.  Mask views in masks_ts order
-    (test.py:425-445): the identity view FIRST, the flipped view, the scales.  With an
-    AUG key off its list is the identity view alone."""
+    its flip with SCALE_H_FLIP), each ASPECT_RATIOS entry (then its flip with
+    ASPECT_RATIO_H_FLIP), the identity view LAST.  Mask views in masks_ts order
+    (test.py:425-456): the identity view FIRST, the flipped view, the scales, the aspect
+    ratios.  An aspect-ratio view is the 4-tuple (TEST.SCALE, TEST.MAX_SIZE, hflip, ar);
+    every other view stays a 3-tuple.  With an AUG key off its list is the identity
+    view alone."""
     tst = cfg.TEST
     ident = (tst.SCALE, tst.MAX_SIZE, False)
 
@@ -290,6 +333,10 @@ def aug_views(cfg):
             v.append((s, aug.MAX_SIZE, False))
             if aug.SCALE_H_FLIP:
                 v.append((s, aug.MAX_SIZE, True))
+        for ar in aug.ASPECT_RATIOS:
+            v.append((tst.SCALE, tst.MAX_SIZE, False, ar))
+            if aug.ASPECT_RATIO_H_FLIP:
+                v.append((tst.SCALE, tst.MAX_SIZE, True, ar))
         return v
 
     box = (extra(tst.BBOX_AUG) if tst.BBOX_AUG.ENABLED else []) + [ident]
@@ -304,8 +351,10 @@ def kps_aug_views(cfg):
     KPS_AUG.SCALES entry the view at (scale, KPS_AUG.MAX_SIZE) and its flip with
     SCALE_H_FLIP.  A scale view is tagged ds when scale < TEST.SCALE and us when
     scale > TEST.SCALE (combine_heatmaps_size_dep drops ds views for small boxes and us
-    views for large ones); the identity and plain-flip views carry neither.  With
-    KPS_AUG off: the identity view alone."""
+    views for large ones); the identity and plain-flip views carry neither.  Then per
+    KPS_AUG.ASPECT_RATIOS entry (test.py:618-628) the 4-tuple (TEST.SCALE, TEST.MAX_SIZE,
+    hflip, ar) and its flip with ASPECT_RATIO_H_FLIP, with neither tag.  With KPS_AUG
+    off: the identity view alone."""
     tst = cfg.TEST
     aug = tst.KPS_AUG
     views, ds, us = [(tst.SCALE, tst.MAX_SIZE, False)], [False], [False]
@@ -320,17 +369,24 @@ def kps_aug_views(cfg):
             views.append((s, aug.MAX_SIZE, hf))
             ds.append(s < tst.SCALE)
             us.append(s > tst.SCALE)
+    for ar in aug.ASPECT_RATIOS:
+        for hf in (False, True) if aug.ASPECT_RATIO_H_FLIP else (False,):
+            views.append((tst.SCALE, tst.MAX_SIZE, hf, ar))
+            ds.append(False)
+            us.append(False)
     return views, ds, us
 
 
 def load_cfg(path: str | None = None, overrides: dict | None = None,
-             test_aug: bool = False) -> AttrDict:
+             test_aug: bool = False, aspect_views: bool = False) -> AttrDict:
     """Defaults, then a reference YAML (safe loader), then dotted overrides.
     Raises NotImplementedError if the result enables an ``UNSUPPORTED`` option.
     test_aug=True accepts TEST.BBOX_AUG.ENABLED / TEST.MASK_AUG.ENABLED (the config
     runs on engine.AugFramePipeline only) and, on a MODEL.KEYPOINTS_ON config,
     TEST.BBOX_AUG.ENABLED / TEST.KPS_AUG.ENABLED (engine.KeypointAugFramePipeline
-    only); it refuses ``UNSUPPORTED_TEST_AUG``."""
+    only); it refuses ``UNSUPPORTED_TEST_AUG``.  aspect_views=True (with test_aug) drops
+    the refusal of the three ASPECT_RATIOS keys (``ASPECT_VIEW_KEYS``) and of nothing
+    else; a non-positive or non-finite ratio raises ValueError."""
     cfg = default_cfg()
     if path:
         with open(path) as f:
@@ -341,7 +397,7 @@ def load_cfg(path: str | None = None, overrides: dict | None = None,
         for p in parts[:-1]:
             d = d[p]
         d[parts[-1]] = val
-    check_supported(cfg, test_aug)
+    check_supported(cfg, test_aug, aspect_views)
     return cfg
 
 

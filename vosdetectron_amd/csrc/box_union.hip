@@ -11,7 +11,8 @@
 //
 // Kernel 1 (vd_box_union_add_view, once per view in vstack order): one workgroup
 //   per (class j >= 1, image): ordered compaction of the view's rows with score >=
-//   thresh, class_nms_kernel's decode + clip, flip_boxes for a flipped view, and
+//   thresh, class_nms_kernel's decode + clip, flip_boxes for a flipped view, the
+//   aspect-ratio view's x * (1 / ar) (vd_box_union_add_view_ar, boxes.py:269-274), and
 //   the rows appended to the class's list behind the earlier views' (the position
 //   is the list's count plus the row's rank in the view, so a list holds the
 //   vstack order: view-major, then proposal index).
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(1024) void union_add_view_kernel(
     const float *__restrict__ rois, const float *__restrict__ cls_prob,
     const float *__restrict__ bbox_pred, const int32_t *__restrict__ roi_count, int R_cap, int K,
     const float *__restrict__ im_scale, const int32_t *__restrict__ im_hw, int hflip,
-    float score_thresh, float4 bbox_w, int cand_cap, UnionWs ws) {
+    int use_x_inv, float x_inv, float score_thresh, float4 bbox_w, int cand_cap, UnionWs ws) {
     __shared__ int scratch[32];
     __shared__ float wts[4];
     const int j = blockIdx.x + 1, img = blockIdx.y;
@@ -127,6 +128,10 @@ __global__ __launch_bounds__(1024) void union_add_view_kernel(
                 const float f1 = (fw - x2) - 1.0f, f2 = (fw - x1) - 1.0f;
                 x1 = f1;
                 x2 = f2;
+            }
+            if (use_x_inv) {  // aspect_ratio(boxes, 1.0 / ar): float32 times the float
+                x1 = x1 * x_inv;
+                x2 = x2 * x_inv;
             }
             c[q] = x1;
             c[(size_t)cand_cap + q] = y1;
@@ -331,10 +336,12 @@ static bool union_args_ok(int cand_cap, int num_images, int K) {
 
 int launch_box_union_add_view(const float *rois, const float *cls_prob, const float *bbox_pred,
                               const int32_t *roi_count, int R_cap, int num_images, int K,
-                              const float *im_scale, const int32_t *im_hw, int hflip, int first,
-                              float score_thresh, const float *bbox_weights, int cand_cap,
-                              void *workspace, size_t ws_bytes, hipStream_t s) {
+                              const float *im_scale, const int32_t *im_hw, int hflip,
+                              int use_x_inv, float x_inv, int first, float score_thresh,
+                              const float *bbox_weights, int cand_cap, void *workspace,
+                              size_t ws_bytes, hipStream_t s) {
     if (!union_args_ok(cand_cap, num_images, K) || R_cap < 1) return VD_ERR_ARG;
+    if (use_x_inv && !(x_inv > 0.f && x_inv < INFINITY)) return VD_ERR_ARG;
     if (cand_cap > kUnionCandMax) return VD_ERR_SHAPE;
     if (!workspace || ws_bytes < box_union_workspace_bytes(cand_cap, num_images, K))
         return VD_ERR_WORKSPACE;
@@ -346,7 +353,7 @@ int launch_box_union_add_view(const float *rois, const float *cls_prob, const fl
     const float4 bw = make_float4(bbox_weights[0], bbox_weights[1], bbox_weights[2], bbox_weights[3]);
     hipLaunchKernelGGL(union_add_view_kernel, dim3(K - 1, num_images), dim3(1024), 0, s, rois,
                        cls_prob, bbox_pred, roi_count, R_cap, K, im_scale, im_hw, hflip ? 1 : 0,
-                       score_thresh, bw, cand_cap, ws);
+                       use_x_inv ? 1 : 0, x_inv, score_thresh, bw, cand_cap, ws);
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 

@@ -499,6 +499,14 @@ int vd_image_resize_to_blob(const uint8_t *frames, int F, int H, int W, const fl
                                  VD_STREAM(stream));
 }
 
+int vd_image_aspect_resize_to_blob(const uint8_t *frames, int F, int H, int W, int War, int hflip,
+                                   const float *lut, double im_scale, int Hr, int Wr, int Hp,
+                                   int Wp, int nhwc, float *blob, void *stream) {
+    if (!frames || !lut || !blob) return VD_ERR_ARG;
+    return launch_aspect_resize_to_blob(frames, F, H, W, War, hflip, lut, im_scale, Hr, Wr, Hp, Wp,
+                                        nhwc, blob, VD_STREAM(stream));
+}
+
 int vd_image_resize_to_blob_ragged(const uint8_t *packed, const VdFrameGeom *geom, int F,
                                    const float *lut, int Hp, int Wp, int nhwc, float *blob,
                                    void *stream) {
@@ -832,9 +840,23 @@ int vd_box_union_add_view(const float *rois, const float *cls_prob, const float 
         !bbox_reg_weights)
         return VD_ERR_ARG;
     return launch_box_union_add_view(rois, cls_prob, bbox_pred, roi_count, R_cap, num_images,
-                                     num_classes, im_scale, im_hw, hflip, first, score_thresh,
-                                     bbox_reg_weights, cand_cap, workspace, workspace_bytes,
-                                     VD_STREAM(stream));
+                                     num_classes, im_scale, im_hw, hflip, 0, 1.0f, first,
+                                     score_thresh, bbox_reg_weights, cand_cap, workspace,
+                                     workspace_bytes, VD_STREAM(stream));
+}
+
+int vd_box_union_add_view_ar(const float *rois, const float *cls_prob, const float *bbox_pred,
+                             const int32_t *roi_count, int R_cap, int num_images, int num_classes,
+                             const float *im_scale, const int32_t *im_hw, int hflip, float x_inv,
+                             int first, float score_thresh, const float *bbox_reg_weights,
+                             int cand_cap, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!rois || !cls_prob || !bbox_pred || !roi_count || !im_scale || !im_hw ||
+        !bbox_reg_weights)
+        return VD_ERR_ARG;
+    return launch_box_union_add_view(rois, cls_prob, bbox_pred, roi_count, R_cap, num_images,
+                                     num_classes, im_scale, im_hw, hflip, 1, x_inv, first,
+                                     score_thresh, bbox_reg_weights, cand_cap, workspace,
+                                     workspace_bytes, VD_STREAM(stream));
 }
 
 int vd_box_union_detections(int cand_cap, int num_images, int num_classes, float nms_thresh,

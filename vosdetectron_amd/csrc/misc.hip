@@ -210,49 +210,62 @@ __device__ __forceinline__ void lut_pixel(const float *slut, const uint8_t *px, 
     v[2] = slut[512 + px[2]];
 }
 
+// The image a resize body reads: px(y, x, u) is pixel (y, x)'s three bytes.
+struct FrameSrc {  // the frame itself
+    const uint8_t *frame;
+    int W;
+    __device__ __forceinline__ void px(int y, int x, uint8_t u[3]) const {
+        const uint8_t *p = frame + ((int64_t)y * W + x) * 3;
+        u[0] = p[0];
+        u[1] = p[1];
+        u[2] = p[2];
+    }
+};
+
 // Both scales exactly 2: OpenCV runs INTER_AREA's fast path instead (mean of
 // each 2 x 2 block, scalar loop order; a partial block at an odd edge
-// averages the taps inside the image)
-__device__ __forceinline__ void area2_pixel(const float *slut, const uint8_t *frame, int H, int W,
+// averages the taps inside the image).  H x W: the image src holds.
+template <class Src>
+__device__ __forceinline__ void area2_pixel(const float *slut, const Src &src, int H, int W,
                                             int y, int x, float v[3]) {
     const int ys = 2 * y, xs = 2 * x;
+    float sum[3] = {0.f, 0.f, 0.f};
+    int cnt = 0;
+    for (int dy = 0; dy < 2 && ys + dy < H; ++dy)
+        for (int dx = 0; dx < 2 && xs + dx < W; ++dx) {
+            uint8_t u[3];
+            src.px(ys + dy, xs + dx, u);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float *L = slut + 256 * c;
-        float sum = 0.f;
-        int cnt = 0;
-        for (int dy = 0; dy < 2 && ys + dy < H; ++dy)
-            for (int dx = 0; dx < 2 && xs + dx < W; ++dx) {
-                sum += L[frame[((int64_t)(ys + dy) * W + xs + dx) * 3 + c]];
-                ++cnt;
-            }
-        v[c] = cnt == 4 ? sum * 0.25f : sum / (float)cnt;
-    }
+            for (int c = 0; c < 3; ++c) sum[c] += slut[256 * c + u[c]];
+            ++cnt;
+        }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = cnt == 4 ? sum[c] * 0.25f : sum[c] / (float)cnt;
 }
 
 struct ResizeRow {  // VResizeLinear taps of one output row
-    const uint8_t *row0, *row1;
+    int r0, r1;
     float b0, b1;
 };
 
-__device__ __forceinline__ ResizeRow resize_row(const uint8_t *frame, int H, int W, int y,
-                                                double scale_y) {
+__device__ __forceinline__ ResizeRow resize_row(int H, int y, double scale_y) {
     ResizeRow r;
     float fy = (float)((y + 0.5) * scale_y - 0.5);
     const int sy = (int)floorf(fy);
     fy -= (float)sy;
-    const int r0 = min(max(sy, 0), H - 1);
-    const int r1 = min(max(sy + 1, 0), H - 1);
-    r.row0 = frame + (int64_t)r0 * W * 3;
-    r.row1 = frame + (int64_t)r1 * W * 3;
+    r.r0 = min(max(sy, 0), H - 1);
+    r.r1 = min(max(sy + 1, 0), H - 1);
     r.b0 = 1.f - fy;
     r.b1 = fy;
     return r;
 }
 
-// HResizeLinear on the two tap rows, then VResizeLinear, per channel
-__device__ __forceinline__ void resize_pixel(const float *slut, const ResizeRow &r, int W, int x,
-                                             double scale_x, float v[3]) {
+// HResizeLinear on the two tap rows, then VResizeLinear, per channel.  W: the
+// width of the image src holds.
+template <class Src>
+__device__ __forceinline__ void resize_pixel(const float *slut, const Src &src,
+                                             const ResizeRow &r, int W, int x, double scale_x,
+                                             float v[3]) {
     float fx = (float)((x + 0.5) * scale_x - 0.5);
     int sx = (int)floorf(fx);
     fx -= (float)sx;
@@ -260,11 +273,16 @@ __device__ __forceinline__ void resize_pixel(const float *slut, const ResizeRow 
     if (sx >= W - 1) { fx = 0.f; sx = W - 1; }
     const int sx1 = min(sx + 1, W - 1);
     const float a0 = 1.f - fx, a1 = fx;
+    uint8_t u00[3], u01[3], u10[3], u11[3];
+    src.px(r.r0, sx, u00);
+    src.px(r.r0, sx1, u01);
+    src.px(r.r1, sx, u10);
+    src.px(r.r1, sx1, u11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float *L = slut + 256 * c;
-        const float d0 = L[r.row0[sx * 3 + c]] * a0 + L[r.row0[sx1 * 3 + c]] * a1;
-        const float d1 = L[r.row1[sx * 3 + c]] * a0 + L[r.row1[sx1 * 3 + c]] * a1;
+        const float d0 = L[u00[c]] * a0 + L[u01[c]] * a1;
+        const float d1 = L[u10[c]] * a0 + L[u11[c]] * a1;
         v[c] = d0 * r.b0 + d1 * r.b1;
     }
 }
@@ -318,20 +336,20 @@ __global__ __launch_bounds__(256) void resize_to_blob_kernel(
     for (int i = threadIdx.x; i < 768; i += blockDim.x) slut[i] = lut[i];
     __syncthreads();
     const int f = blockIdx.z, y = blockIdx.y;
-    const uint8_t *frame = frames + (int64_t)f * H * W * 3;
+    const FrameSrc src = {frames + (int64_t)f * H * W * 3, W};
     if (scale_x == 2.0 && scale_y == 2.0) {  // area2_pixel
         for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
             float v[3] = {0.f, 0.f, 0.f};
-            if (y < Hr && x < Wr) area2_pixel(slut, frame, H, W, y, x, v);
+            if (y < Hr && x < Wr) area2_pixel(slut, src, H, W, y, x, v);
             blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
         }
         return;
     }
-    ResizeRow r = {frame, frame, 0.f, 0.f};
-    if (y < Hr) r = resize_row(frame, H, W, y, scale_y);
+    ResizeRow r = {0, 0, 0.f, 0.f};
+    if (y < Hr) r = resize_row(H, y, scale_y);
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
         float v[3] = {0.f, 0.f, 0.f};
-        if (y < Hr && x < Wr) resize_pixel(slut, r, W, x, scale_x, v);
+        if (y < Hr && x < Wr) resize_pixel(slut, src, r, W, x, scale_x, v);
         blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
     }
 }
@@ -345,6 +363,93 @@ int launch_resize_to_blob(const uint8_t *frames, int F, int H, int W, const floa
     dim3 grid((Wp + 255) / 256, Hp, F);
     hipLaunchKernelGGL(resize_to_blob_kernel, grid, dim3(256), 0, s, frames, H, W, lut, scale,
                        scale, Hr, Wr, Hp, Wp, nhwc, blob);
+    return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
+}
+
+// An aspect-ratio view of the test-time augmentation (lib/core/test.py:330-363,
+// 509-526, 684-702): im_ar = cv2.resize(im, dsize=(War, H)) (lib/utils/image.py:
+// 27-32), a u8 -> u8 INTER_LINEAR resize of the width alone, then prep_im_for_blob
+// of im_ar as above.  im_ar is never stored: AspectSrc synthesises each of its
+// pixels that a body taps from the two horizontally adjacent bytes of the frame.
+// It restates OpenCV's 8-bit INTER_LINEAR path with dsize given (fixed point,
+// INTER_RESIZE_COEF_SCALE = 2048):
+//   scale = 1.0 / ((double)War / W)                      (`scale1`, from the host)
+//   fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), fx -= sx;
+//   sx < 0 -> (0, 0); sx >= W-1 -> (W-1, 0)
+//   a0 = rint((1.f - fx) * 2048), a1 = rint(fx * 2048)   (int16, half to even,
+//                                                          each on its own)
+//   D = S[sx] * a0 + S[min(sx+1, W-1)] * a1              (HResizeLinear, int32)
+//   out = (uint8)(((D >> 9) + 2) >> 2)                   (VResizeLinear with the
+//                                  unchanged height's coefficients (2048, 0))
+// A flipped view is im_ar[:, ::-1]: column x reads im_ar's column War - 1 - x (the
+// reference flips after resizing; the two coefficients round independently, so
+// resizing the flipped frame need not give the same bytes).  The per-column
+// (sx, a0, a1) are recomputed by every thread that taps the column: one double
+// multiply and a few conversions beside a pixel's 12 stored bytes, against a
+// per-block table that would cost an LDS pass and a barrier for <= 2 uses per
+// entry.  As with the float resize, parity against an executed cv2 is unpinned
+// (cv2 absent); the kernel is pinned against the numpy restatement and known
+// answers.
+struct AspectSrc {
+    const uint8_t *frame;
+    int W, War, flip;
+    double scale1;
+    __device__ __forceinline__ void px(int y, int x, uint8_t u[3]) const {
+        if (flip) x = War - 1 - x;
+        float fx = (float)((x + 0.5) * scale1 - 0.5);
+        int sx = (int)floorf(fx);
+        fx -= (float)sx;
+        if (sx < 0) { fx = 0.f; sx = 0; }
+        if (sx >= W - 1) { fx = 0.f; sx = W - 1; }
+        const int a0 = (int)rintf((1.f - fx) * 2048.f), a1 = (int)rintf(fx * 2048.f);
+        const uint8_t *row = frame + (int64_t)y * W * 3;
+        const uint8_t *p0 = row + sx * 3, *p1 = row + min(sx + 1, W - 1) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int D = (int)p0[c] * a0 + (int)p1[c] * a1;
+            u[c] = (uint8_t)(((D >> 9) + 2) >> 2);
+        }
+    }
+};
+
+// resize_to_blob_kernel on im_ar (H x War), one launch per view.
+__global__ __launch_bounds__(256) void aspect_resize_to_blob_kernel(
+    const uint8_t *__restrict__ frames, int H, int W, int War, int flip, double scale1,
+    const float *__restrict__ lut, double scale, int Hr, int Wr, int Hp, int Wp, int nhwc,
+    float *__restrict__ blob) {
+    __shared__ float slut[768];
+    for (int i = threadIdx.x; i < 768; i += blockDim.x) slut[i] = lut[i];
+    __syncthreads();
+    const int f = blockIdx.z, y = blockIdx.y;
+    const AspectSrc src = {frames + (int64_t)f * H * W * 3, W, War, flip, scale1};
+    if (scale == 2.0) {  // area2_pixel
+        for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
+            float v[3] = {0.f, 0.f, 0.f};
+            if (y < Hr && x < Wr) area2_pixel(slut, src, H, War, y, x, v);
+            blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
+        }
+        return;
+    }
+    ResizeRow r = {0, 0, 0.f, 0.f};
+    if (y < Hr) r = resize_row(H, y, scale);
+    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
+        float v[3] = {0.f, 0.f, 0.f};
+        if (y < Hr && x < Wr) resize_pixel(slut, src, r, War, x, scale, v);
+        blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
+    }
+}
+
+int launch_aspect_resize_to_blob(const uint8_t *frames, int F, int H, int W, int War, int hflip,
+                                 const float *lut, double im_scale, int Hr, int Wr, int Hp,
+                                 int Wp, int nhwc, float *blob, hipStream_t s) {
+    if (F < 1 || H < 1 || W < 1 || War < 1 || !(im_scale > 0.0) || Hr < 1 || Wr < 1 || Hp < Hr ||
+        Wp < Wr || Hp > 65535 || F > 65535)
+        return VD_ERR_ARG;
+    const double scale1 = 1.0 / ((double)War / W);  // cv::resize with dsize: inv = War / W
+    const double scale = 1.0 / im_scale;
+    dim3 grid((Wp + 255) / 256, Hp, F);
+    hipLaunchKernelGGL(aspect_resize_to_blob_kernel, grid, dim3(256), 0, s, frames, H, W, War,
+                       hflip ? 1 : 0, scale1, lut, scale, Hr, Wr, Hp, Wp, nhwc, blob);
     return hipGetLastError() == hipSuccess ? VD_OK : VD_ERR_LAUNCH;
 }
 
@@ -386,16 +491,17 @@ __global__ __launch_bounds__(256) void resize_to_blob_ragged_kernel(
     if (scale == 2.0) {  // area2_pixel
         for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
             float v[3] = {0.f, 0.f, 0.f};
-            if (y < Hr && x < Wr) area2_pixel(slut, frame, H, W, y, x, v);
+            if (y < Hr && x < Wr) area2_pixel(slut, FrameSrc{frame, W}, H, W, y, x, v);
             blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
         }
         return;
     }
-    ResizeRow r = {frame, frame, 0.f, 0.f};
-    if (y < Hr) r = resize_row(frame, H, W, y, scale);
+    const FrameSrc src = {frame, W};
+    ResizeRow r = {0, 0, 0.f, 0.f};
+    if (y < Hr) r = resize_row(H, y, scale);
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Wp; x += gridDim.x * blockDim.x) {
         float v[3] = {0.f, 0.f, 0.f};
-        if (y < Hr && x < Wr) resize_pixel(slut, r, W, x, scale, v);
+        if (y < Hr && x < Wr) resize_pixel(slut, src, r, W, x, scale, v);
         blob_store(blob, f, y, x, Hp, Wp, nhwc, v);
     }
 }

@@ -163,6 +163,9 @@ int launch_image_to_blob(const uint8_t *frames, int F, int H, int W, const float
 int launch_resize_to_blob(const uint8_t *frames, int F, int H, int W, const float *lut,
                           double im_scale, int Hr, int Wr, int Hp, int Wp, int nhwc, float *blob,
                           hipStream_t s);
+int launch_aspect_resize_to_blob(const uint8_t *frames, int F, int H, int W, int War, int hflip,
+                                 const float *lut, double im_scale, int Hr, int Wr, int Hp,
+                                 int Wp, int nhwc, float *blob, hipStream_t s);
 int launch_resize_to_blob_ragged(const uint8_t *packed, const VdFrameGeom *geom, int F,
                                  const float *lut, int Hp, int Wp, int nhwc, float *blob,
                                  hipStream_t s);
@@ -263,9 +266,10 @@ int launch_detections_postfilter(float *dets, int32_t *cls, int32_t *counts, int
 size_t box_union_workspace_bytes(int cand_cap, int num_images, int num_classes);
 int launch_box_union_add_view(const float *rois, const float *cls_prob, const float *bbox_pred,
                               const int32_t *roi_count, int R_cap, int num_images, int K,
-                              const float *im_scale, const int32_t *im_hw, int hflip, int first,
-                              float score_thresh, const float *bbox_weights, int cand_cap,
-                              void *workspace, size_t ws_bytes, hipStream_t s);
+                              const float *im_scale, const int32_t *im_hw, int hflip,
+                              int use_x_inv, float x_inv, int first, float score_thresh,
+                              const float *bbox_weights, int cand_cap, void *workspace,
+                              size_t ws_bytes, hipStream_t s);
 int launch_box_union_detections(int cand_cap, int num_images, int K, float nms_thresh,
                                 int dets_per_im, int soft_method, float soft_sigma, float soft_min,
                                 int vote_method, float vote_th, float vote_beta, int det_cap,

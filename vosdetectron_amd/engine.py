@@ -79,11 +79,31 @@ class _ViewGeom:
     identity view of a plain step or a test-time-augmentation view (lib/utils/blob.py:
     37-161): get_target_scale, cv2.resize to round(H*s) x round(W*s) (done on the device
     when s != 1), pad to `stride` (get_max_shape), and the per-frame rows the proposal,
-    detection and RoI kernels read -- the fields a RaggedBatch carries per frame."""
+    detection and RoI kernels read -- the fields a RaggedBatch carries per frame.
+
+    An aspect-ratio view (scale, max_size, hflip, ar) (lib/core/test.py:330-363) is the
+    geometry of im_ar, the frame with its width resized to War = int(round(ar * W))
+    (lib/utils/image.py:27-32): scale, Hr / Wr / Hp / Wp and im_hw = (H, War) come from
+    (H, War); ar is the ratio (None on any other view), x_inv = float32(1.0 / ar) the
+    factor that maps the view's boxes back, flip_w the width a flip of the view's boxes
+    uses (War; W on any other view)."""
 
     def __init__(self, view, H, W, stride, F, device):
         self.view, self.F = view, F
         self.hflip = bool(view[2])
+        self.ar = float(view[3]) if len(view) > 3 else None
+        self.x_inv = None
+        if self.ar is not None:
+            if not (self.ar > 0.0 and math.isfinite(self.ar)):
+                raise ValueError("aspect-ratio view %r: the ratio is not a positive finite "
+                                 "number" % (view,))
+            War = ops.aspect_width(W, self.ar)
+            if War < 2:
+                raise ValueError("aspect-ratio view %r: at frame width %d the view is %d "
+                                 "column(s) wide, under 2" % (view, W, War))
+            self.x_inv = float(np.float32(1.0 / self.ar))
+            W = War
+        self.flip_w = W
         self.scale = ops.target_scale(H, W, view[0], view[1])
         self.Hr, self.Wr = ops.resized_hw(H, W, self.scale)
         self.Hp = int(math.ceil(self.Hr / stride) * stride)
@@ -103,6 +123,27 @@ class _ViewGeom:
         for k in ("im_info", "im_scale_t", "im_scale_d", "im_hw"):
             setattr(g, k, getattr(self, k)[:F])
         return g
+
+
+def _flip_dets(dets, width):
+    """flip_boxes of detections [..., >= 4], float32: x1' = (width - x2) - 1."""
+    dets_hf = dets.clone()
+    dets_hf[..., 0] = width - dets[..., 2] - 1
+    dets_hf[..., 2] = width - dets[..., 0] - 1
+    return dets_hf
+
+
+def view_dets(dets, g):
+    """Detections [..., >= 4] as the heads of view g (a _ViewGeom) take them
+    (lib/core/test.py:485, 513-518): aspect_ratio(boxes, ar) for an aspect-ratio view
+    (float32 x1, x2 times float32(ar)), then flip_boxes with the view's width for a
+    flipped one.  In torch, on the detections' device."""
+    if g.ar is not None:
+        dets_ar = dets.clone()
+        dets_ar[..., 0] = g.ar * dets[..., 0]
+        dets_ar[..., 2] = g.ar * dets[..., 2]
+        dets = dets_ar
+    return _flip_dets(dets, g.flip_w) if g.hflip else dets
 
 
 class FramePipeline:
@@ -204,10 +245,14 @@ class FramePipeline:
     def make_blob(self, frames, g=None):
         """get_image_blob on the device at view geometry g (None: the pipeline's own):
         identity scale -> vd_image_to_blob, else vd_image_resize_to_blob (mean
-        subtraction + INTER_LINEAR resize + pad)."""
+        subtraction + INTER_LINEAR resize + pad).  An aspect-ratio view takes the
+        UNFLIPPED frames: vd_image_aspect_resize_to_blob resizes the width, then flips."""
         nhwc = self.channels_last
         scale, Hp, Wp = (self.im_scale, self.Hp, self.Wp) if g is None else (g.scale, g.Hp, g.Wp)
-        if scale == 1.0:
+        if g is not None and g.ar is not None:
+            blob = ops.image_aspect_resize_to_blob(frames, self.lut, g.ar, scale, Hp, Wp,
+                                                   hflip=g.hflip, nhwc=nhwc)
+        elif scale == 1.0:
             blob = ops.image_to_blob(frames, self.lut, Hp, Wp, nhwc=nhwc)
         else:
             blob = ops.image_resize_to_blob(frames, self.lut, scale, Hp, Wp, nhwc=nhwc)
@@ -336,25 +381,25 @@ class FramePipeline:
 
     def _hflip_dets(self, dets):
         """flip_boxes of the detections, float32: x1' = (W - x2) - 1."""
-        dets_hf = dets.clone()
-        dets_hf[..., 0] = self.W - dets[..., 2] - 1
-        dets_hf[..., 2] = self.W - dets[..., 0] - 1
-        return dets_hf
+        return _flip_dets(dets, self.W)
 
     def _view_rois(self, out, src, rows, row0=0):
         """Rows [row0, row0 + rows) of the RoI batch of src's detections (dets, classes,
         counts), once per head view: yields (view, (RoIs at the view's scale, levels,
         classes, device total), pyramid, fast).  The batch is F x DETECTIONS_PER_IM rows
         built on the device from the device counts -- no host read inside the step; a
-        flipped view takes flip_boxes of the detections, made once."""
+        flipped or aspect-ratio view takes flip_boxes / aspect_ratio of the detections,
+        made once per distinct (ar, hflip)."""
         cfg = self.cfg
         dets, dcls, dcnt = src["dets"], src["classes"], src["counts"]
-        dets_hf = None
+        made = {(None, False): dets}
         for v in self.head_views:
             g, pyr, fast = out["_pyrs"][v]
-            if v[2] and dets_hf is None:
-                dets_hf = self._hflip_dets(dets)
-            yield v, ops.mask_rois(dets_hf if v[2] else dets, dcls, dcnt, g.im_scale_d, rows,
+            key = (v[3] if len(v) > 3 else None, bool(v[2]))
+            if key not in made:
+                made[key] = view_dets(dets, g) if key[0] is not None \
+                    else self._hflip_dets(dets)
+            yield v, ops.mask_rois(made[key], dcls, dcnt, g.im_scale_d, rows,
                                    cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL, row0=row0), \
                 pyr, fast
 
@@ -688,8 +733,9 @@ class _AugViews:
         return self._unions[(F, K)]
 
     def _view_body(self, frames, flipped, g):
-        """View g's blob, of the frames or their horizontal flip, and its body."""
-        blob = self.make_blob(flipped if g.hflip else frames, g)
+        """View g's blob, of the frames or their horizontal flip, and its body (an
+        aspect-ratio view's flip is an argument of its blob kernel)."""
+        blob = self.make_blob(flipped if g.hflip and g.ar is None else frames, g)
         return blob, self.model.Conv_Body(blob)
 
     def _box_pass(self, frames, keep_intermediates=False):
@@ -697,7 +743,7 @@ class _AugViews:
         of the head views it did not run (the reference's im_conv_body_only).  A head
         view keeps its pyramid for the head pass; keep_intermediates adds out["views"]."""
         F = frames.shape[0]
-        flipped = frames.flip(2) if any(v[2] for v in self.geom) else None
+        flipped = frames.flip(2) if any(v[2] and len(v) == 3 for v in self.geom) else None
         views = {}
         if self.box_union:
             out = self._union_pass(frames, flipped, views, keep_intermediates)
@@ -732,7 +778,7 @@ class _AugViews:
             union = union or self._union(F, K)
             union.add_view(rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
                            g.im_scale_t, g.im_hw, g.hflip, tst.SCORE_THRESH,
-                           cfg.MODEL.BBOX_REG_WEIGHTS, first=i == 0)
+                           cfg.MODEL.BBOX_REG_WEIGHTS, first=i == 0, x_inv=g.x_inv)
             self._mark("union_add_view")
             if v in self.head_views:
                 pyrs[v] = (g, pyr, fast)
@@ -764,8 +810,10 @@ class AugFramePipeline(_AugViews, FramePipeline):
     TEST.MASK_AUG, lib/core/test.py:193-363, 405-526) for the FPN mask configs and
     frames of one size; cfg comes from config.load_cfg(..., test_aug=True).
 
-      per distinct view (config.aug_views: scale, max_size, hflip), on the frames or
-      their horizontal flip: blob at the view's geometry --> body --> [box views: RPN,
+      per distinct view (config.aug_views: scale, max_size, hflip[, ar]), on the frames
+      or their horizontal flip (an aspect-ratio view: vd_image_aspect_resize_to_blob on
+      the frames, its boxes mapped back by x_inv in the union and its heads' detections
+      by aspect_ratio): blob at the view's geometry --> body --> [box views: RPN,
       proposals, collect, box RoIAlign, box head --> vd_box_union_add_view in np.vstack
       order, the identity view last]
       --> vd_box_union_detections (UNION heuristics: one box_results_with_nms_and_limit
@@ -794,7 +842,8 @@ class AugFramePipeline(_AugViews, FramePipeline):
                 "AugFramePipeline: FPN mask configs only (test-time augmentation on the C4, "
                 "VOS and keypoint pipelines is not built; keypoint configs run on "
                 "KeypointAugFramePipeline)")
-        vcfg.check_supported(cfg, test_aug=True)
+        vcfg.check_supported(cfg, test_aug=True, aspect_views=True)
+        vcfg.check_aspect_ratios(cfg, frame_hw[1])
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device)
         box_views, self.mask_views = vcfg.aug_views(cfg)
         self.mask_heur = cfg.TEST.MASK_AUG.HEUR if cfg.TEST.MASK_AUG.ENABLED else "SOFT_AVG"
@@ -838,7 +887,8 @@ class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
                  det_cap=256, device="cuda", nms_oks=None, cand_cap=None,
                  pyramid_budget_bytes=24 << 30, heatmap_budget_bytes=8 << 30):
         from . import config as vcfg
-        vcfg.check_supported(cfg, test_aug=True)
+        vcfg.check_supported(cfg, test_aug=True, aspect_views=True)
+        vcfg.check_aspect_ratios(cfg, frame_hw[1])
         super().__init__(model, cfg, frame_hw, batch, channels_last, det_cap, device, nms_oks)
         tst = cfg.TEST
         self.bbox_aug = self.box_union = bool(tst.BBOX_AUG.ENABLED)

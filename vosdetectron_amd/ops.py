@@ -1186,6 +1186,37 @@ def image_resize_to_blob(frames: torch.Tensor, lut: torch.Tensor, im_scale: floa
     return out
 
 
+def aspect_width(im_w: int, ar: float) -> int:
+    """lib/utils/image.py:30: int(round(aspect_ratio * im_w)), Python's round of the
+    float64 product (half to even)."""
+    return int(round(float(ar) * im_w))
+
+
+def image_aspect_resize_to_blob(frames: torch.Tensor, lut: torch.Tensor, ar: float,
+                                im_scale: float, Hp: int, Wp: int, hflip: bool = False,
+                                nhwc: bool = False, out: Optional[torch.Tensor] = None):
+    """The blob of an aspect-ratio view in one launch (vd_image_aspect_resize_to_blob):
+    aspect_ratio_rel's u8 width resize to War = aspect_width(W, ar), the horizontal
+    flip of that image when hflip (pass the UNFLIPPED frames), then prep_im_for_blob +
+    im_list_to_blob at im_scale.  The u8 image is never written."""
+    fr = _need(frames, "frames", torch.uint8)
+    F, H, W, three = fr.shape
+    War = aspect_width(W, ar)
+    if War < 1:
+        raise ValueError("aspect ratio %r of width %d leaves no column" % (ar, W))
+    Hr, Wr = resized_hw(H, War, im_scale)
+    if Hp < Hr or Wp < Wr:
+        raise ValueError("blob %dx%d smaller than the resized frame %dx%d" % (Hp, Wp, Hr, Wr))
+    lt = _need(lut, "lut")
+    if out is None:
+        shape = (F, Hp, Wp, 3) if nhwc else (F, 3, Hp, Wp)
+        out = torch.empty(shape, dtype=torch.float32, device=fr.device)
+    check(lib().vd_image_aspect_resize_to_blob(
+        fr.data_ptr(), F, H, W, War, int(bool(hflip)), lt.data_ptr(), float(im_scale), Hr, Wr,
+        Hp, Wp, int(nhwc), out.data_ptr(), _stream()), "vd_image_aspect_resize_to_blob")
+    return out
+
+
 # ---- frames of different sizes in one blob (vd_image_resize_to_blob_ragged)
 GEOM_DTYPE = np.dtype([("offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("Hr", "<i4"),
                        ("Wr", "<i4"), ("inv_scale", "<f8")])  # struct VdFrameGeom
@@ -1475,10 +1506,13 @@ class BoxUnion:
         self.views = 0
 
     def add_view(self, rois, cls_prob, bbox_pred, roi_count, im_scale, im_hw, hflip: bool,
-                 score_thresh=0.05, bbox_reg_weights=(10., 10., 5., 5.), first=None):
+                 score_thresh=0.05, bbox_reg_weights=(10., 10., 5., 5.), first=None,
+                 x_inv=None):
         """One view's rois [F,R,5], cls_prob [F,R,K], bbox_pred [F,R,4K], roi_count [F],
         its im_scale [F] fp32 and the ORIGINAL frames' im_hw [F,2] int32.  first (default:
-        the first call after construction or detections()) empties the lists."""
+        the first call after construction or detections()) empties the lists.  x_inv: an
+        aspect-ratio view's float32(1.0 / ar) (vd_box_union_add_view_ar: im_hw is then
+        the view's (H, War), and x1, x2 are multiplied by x_inv after the flip-back)."""
         r = _need(rois, "rois")
         p = _need(cls_prob, "cls_prob")
         d = _need(bbox_pred, "bbox_pred")
@@ -1494,11 +1528,18 @@ class BoxUnion:
                                          self.K))
         first = self.views == 0 if first is None else bool(first)
         w = (ctypes.c_float * 4)(*[float(np.float32(x)) for x in bbox_reg_weights])
-        check(lib().vd_box_union_add_view(
-            r.data_ptr(), p.data_ptr(), d.data_ptr(), c.data_ptr(), R, N, K, s.data_ptr(),
-            hw.data_ptr(), int(bool(hflip)), int(first), float(np.float32(score_thresh)),
-            ctypes.cast(w, ctypes.c_void_p), self.cand_cap, self.ws.data_ptr(), self.ws.numel(),
-            _stream()), "vd_box_union_add_view")
+        if x_inv is None:
+            check(lib().vd_box_union_add_view(
+                r.data_ptr(), p.data_ptr(), d.data_ptr(), c.data_ptr(), R, N, K, s.data_ptr(),
+                hw.data_ptr(), int(bool(hflip)), int(first), float(np.float32(score_thresh)),
+                ctypes.cast(w, ctypes.c_void_p), self.cand_cap, self.ws.data_ptr(),
+                self.ws.numel(), _stream()), "vd_box_union_add_view")
+        else:
+            check(lib().vd_box_union_add_view_ar(
+                r.data_ptr(), p.data_ptr(), d.data_ptr(), c.data_ptr(), R, N, K, s.data_ptr(),
+                hw.data_ptr(), int(bool(hflip)), float(np.float32(x_inv)), int(first),
+                float(np.float32(score_thresh)), ctypes.cast(w, ctypes.c_void_p), self.cand_cap,
+                self.ws.data_ptr(), self.ws.numel(), _stream()), "vd_box_union_add_view_ar")
         self.views = 1 if first else self.views + 1
 
     def detections(self, nms_thresh=0.5, dets_per_im=100, det_cap=256, out=None,
