@@ -594,14 +594,13 @@ int vd_group_norm_act(const float *x, const float *x2, int B, int C, int H, int 
                       float eps, const float *gamma, const float *beta, const float *residual,
                       int residual_mode, const float *res_gamma, const float *res_beta, int act,
                       int layout, float *out, void *workspace, size_t ws_bytes, void *stream) {
-    if (bad_gn(x, B, C, H, W, G, layout) || !gamma || !beta || !out || !workspace)
-        return VD_ERR_ARG;
+    if (bad_gn(x, B, C, H, W, G, layout) || !gamma || !beta || !out) return VD_ERR_ARG;
     if (residual_mode < 0 || residual_mode > 3 || act < 0 || act > 3) return VD_ERR_ARG;
     if (residual_mode && !residual) return VD_ERR_ARG;
     if (residual_mode == 3 && (!res_gamma || !res_beta)) return VD_ERR_ARG;
     if (residual_mode == 2 && ((H & 1) || (W & 1))) return VD_ERR_SHAPE;
     const int nsets = residual_mode == 3 ? 2 : 1;
-    if (ws_bytes < gn_workspace_bytes(B, G, nsets)) return VD_ERR_WORKSPACE;
+    if (!workspace || ws_bytes < gn_workspace_bytes(B, G, nsets)) return VD_ERR_WORKSPACE;
     double *ws = static_cast<double *>(workspace);
     const size_t per = (size_t)B * G * 2;
     GnSets sets = {};
@@ -634,10 +633,9 @@ int vd_convgru_gates(const float *zh, const float *zx, const float *rh, const fl
                      const float *gamma_z, const float *beta_z, const float *gamma_r,
                      const float *beta_r, int layout, float *z, float *hr, void *workspace,
                      size_t ws_bytes, void *stream) {
-    if (bad_gn(zx, B, C, H, W, G, layout) || !gamma_z || !beta_z || !z || !workspace)
-        return VD_ERR_ARG;
+    if (bad_gn(zx, B, C, H, W, G, layout) || !gamma_z || !beta_z || !z) return VD_ERR_ARG;
     if (h && (!zh || !rh || !rx || !gamma_r || !beta_r || !hr)) return VD_ERR_ARG;
-    if (ws_bytes < gn_workspace_bytes(B, G, 2)) return VD_ERR_WORKSPACE;
+    if (!workspace || ws_bytes < gn_workspace_bytes(B, G, 2)) return VD_ERR_WORKSPACE;
     double *ws = static_cast<double *>(workspace);
     const size_t per = (size_t)B * G * 2;
     GnSets sets = {};
@@ -673,10 +671,9 @@ int vd_convgru_update(const float *hh, const float *hx, const float *z, const fl
                       const float *finer, int B, int C, int H, int W, int G, float eps,
                       const float *gamma_h, const float *beta_h, int layout, float *out,
                       void *workspace, size_t ws_bytes, void *stream) {
-    if (bad_gn(hx, B, C, H, W, G, layout) || !z || !gamma_h || !beta_h || !out || !workspace)
-        return VD_ERR_ARG;
+    if (bad_gn(hx, B, C, H, W, G, layout) || !z || !gamma_h || !beta_h || !out) return VD_ERR_ARG;
     if (h && !hh) return VD_ERR_ARG;
-    if (ws_bytes < gn_workspace_bytes(B, G, 1)) return VD_ERR_WORKSPACE;
+    if (!workspace || ws_bytes < gn_workspace_bytes(B, G, 1)) return VD_ERR_WORKSPACE;
     GnSets sets = {};
     sets.s[0] = {hx, h ? hh : nullptr, static_cast<double *>(workspace)};
     hipStream_t s = VD_STREAM(stream);

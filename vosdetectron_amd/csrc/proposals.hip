@@ -68,8 +68,10 @@ static bool rpn_plan(const VdRpnLevel *levels, int num_levels, int pre_nms_topN,
         const int n_all = levels[l].A * levels[l].H * levels[l].W;
         const bool take_all = pre_nms_topN <= 0 || pre_nms_topN >= n_all;
         const int pre = take_all ? n_all : pre_nms_topN;
-        if (pre > kPreMax || (take_all && n_all > kSelCap)) *large = true;
-        if (pre > kPreMaxL || (take_all && n_all > kSelCapL)) return false;
+        // take-all makes pre = n_all, so these two tests also cover a take-all level past
+        // the candidate capacities (kSelCap >= kPreMax, kSelCapL >= kPreMaxL)
+        if (pre > kPreMax) *large = true;
+        if (pre > kPreMaxL) return false;
         *max_pre = pre > *max_pre ? pre : *max_pre;
     }
     return true;
@@ -859,7 +861,9 @@ int launch_rpn_proposals(const VdRpnLevel *levels, int num_levels, int num_image
     const size_t mb = rpn_mask_bytes(p);
     const size_t bb = split ? rpn_box_bytes(p) : 0;
     const size_t sb = rpn_slot_bytes(max_pre, split);
-    if (!workspace || ws_bytes < sb * (size_t)num_levels * (size_t)num_images)
+    // the caller's size is the size function's, not the sum of the parts used below
+    if (!workspace ||
+        ws_bytes < rpn_workspace_bytes(levels, num_levels, num_images, pre_nms_topN))
         return VD_ERR_WORKSPACE;
     const dim3 grid(num_levels, num_images);
     // multi-workgroup select of every slot that keeps fewer than all its anchors
@@ -878,7 +882,6 @@ int launch_rpn_proposals(const VdRpnLevel *levels, int num_levels, int num_image
         const int cap = rpn_sel_cap(max_pre, large);
         selb = sel_slot_bytes(cap);
         const size_t slots = (size_t)num_levels * (size_t)num_images;
-        if (ws_bytes < sb * slots + selb * slots) return VD_ERR_WORKSPACE;
         char *sw = (char *)workspace + sb * slots;
         sel_ws = sw;
         if (nch > 0) {

@@ -180,7 +180,7 @@ def roi_align_fpn(levels: Sequence[torch.Tensor], spatial_scales: Sequence[float
         L = len(levels)
         nws = lib().vd_roi_align_fpn_tiled_workspace_size(descs, L, B, C, R, resolution)
         if nws:
-            ws = torch.empty((nws,), dtype=torch.uint8, device=r.device)
+            ws = _ws(nws, r.device)
             st = lib().vd_roi_align_fpn_tiled_forward(
                 descs, L, B, C, r.data_ptr(), lv.data_ptr() if lv is not None else None, R,
                 resolution, 2, out.data_ptr(), ws.data_ptr(), nws, _stream())
