@@ -871,6 +871,49 @@ int vd_segm_rle_ragged(const float *masks, int M, int R, const float *boxes, int
                        int32_t *ncounts, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * viz_mask_result (lib/utils/vis.py:119-157, called per frame from
+ * lib_vos/tools/train_davis_online.py:596-600) on the device: the object-ID
+ * image of every frame of a step, without the per-detection planes.
+ *
+ * vd_label_maps: masks rows of R x R fp32 (class-selected probabilities) in
+ * (frame, detection) order -- the row of detection (f, i) is
+ * sum(clamp(counts[0..f), 0, cap)) + i, formed on the device (no host read, so
+ * the call is valid on counts that are still being computed on the stream and
+ * can be graph-captured); masks must hold sum(clamp(counts, 0, cap)) rows.
+ * dets F x cap x 5 fp32 (x1, y1, x2, y2, score), classes F x cap int32, counts
+ * F int32 (device), valid F x cap u8 or NULL (rows a post-filter kept).  A count
+ * outside [0, cap] is clamped; nothing outside the buffers is read or written
+ * whatever counts holds.
+ *
+ * Detection i of frame f is painted iff i < counts[f], (valid == NULL or
+ * valid[f][i] != 0) and !(score < score_thresh), compared in float32: that is
+ * how NumPy >= 2 evaluates `np.float32 < python float` (NEP 50), i.e. the
+ * reference's `score < thresh` with the threshold rounded to float32 first.
+ * label[f][y][x] = the written id of the painted detection with the highest
+ * score whose pasted, binarised mask (vd_paste_masks' value at bin_thresh, bit
+ * for bit) covers (x, y), 0 where none does: the reference's painting in
+ * ascending score order.  Among equal scores the higher row index is painted
+ * later and wins (the reference's np.argsort is not stable; this is the
+ * project's rule).  gt[f][y][x] = label[f][y][x] where the winner's
+ * score > gt_thresh (float32), else 0: rtv_gt at rvt_cls_threshold = gt_thresh.
+ * The written id of class c is lut[c] (c in [0, lut_n)), or c itself (c in
+ * [0, 255]) when lut is NULL; any other class writes 0.  label and gt are
+ * F x im_h x im_w u8, every byte written; gt may be NULL.
+ *
+ * R in 1..62, im_h, im_w >= 1, 1 <= cap <= 1024, F <= 65535, im_h <= 2097120
+ * (VD_ERR_SHAPE otherwise); workspace_bytes >= vd_label_maps_workspace_size(F,
+ * cap) (VD_ERR_WORKSPACE; the size is 0 for an F or cap the kernel refuses),
+ * 16-byte aligned; NULL masks / dets / classes / counts / label / workspace or a
+ * lut with lut_n < 1 give VD_ERR_ARG.  Nothing is launched on an error.
+ * ------------------------------------------------------------------------- */
+size_t vd_label_maps_workspace_size(int F, int cap);
+int vd_label_maps(const float *masks, int R, const float *dets, const int32_t *classes,
+                  const int32_t *counts, const uint8_t *valid, int F, int cap, int im_h, int im_w,
+                  float bin_thresh, float score_thresh, float gt_thresh, const uint8_t *lut,
+                  int lut_n, uint8_t *label, uint8_t *gt, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * keypoint_results' heatmap decode (lib/utils/keypoints.py:103-157
  * heatmaps_to_keypoints with scores_to_probs :214-222; called from
  * lib/core/test.py:858-874) on the device.

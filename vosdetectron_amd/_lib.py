@@ -154,6 +154,10 @@ SIGNATURES = {
     "vd_segm_rle": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P, _I, _P, _P]),
     "vd_segm_rle_ragged": (_I, [_P, _I, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "vd_rle_strings": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    # viz_mask_result (per-frame object-ID maps)
+    "vd_label_maps_workspace_size": (_S, [_I, _I]),
+    "vd_label_maps": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _I, _P, _P,
+                           _P, _S, _P]),
     # keypoint_results (heatmap decode)
     "vd_heatmaps_to_keypoints": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     # im_detect_keypoints_aug's combination fused into the decode

@@ -742,6 +742,21 @@ int vd_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, int ca
     return launch_rle_strings(counts, ncounts, M, cap, lens, chars, VD_STREAM(stream));
 }
 
+size_t vd_label_maps_workspace_size(int F, int cap) { return label_maps_workspace_bytes(F, cap); }
+
+int vd_label_maps(const float *masks, int R, const float *dets, const int32_t *classes,
+                  const int32_t *counts, const uint8_t *valid, int F, int cap, int im_h, int im_w,
+                  float bin_thresh, float score_thresh, float gt_thresh, const uint8_t *lut,
+                  int lut_n, uint8_t *label, uint8_t *gt, void *workspace,
+                  size_t workspace_bytes, void *stream) {
+    if (F == 0) return VD_OK;
+    if (!masks || !dets || !classes || !counts || !label || F < 0 || (lut && lut_n < 1))
+        return VD_ERR_ARG;
+    return launch_label_maps(masks, R, dets, classes, counts, valid, F, cap, im_h, im_w,
+                             bin_thresh, score_thresh, gt_thresh, lut, lut_n, label, gt,
+                             workspace, workspace_bytes, VD_STREAM(stream));
+}
+
 int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                              int box_stride, int min_size, float *out, void *stream) {
     if (R == 0) return VD_OK;

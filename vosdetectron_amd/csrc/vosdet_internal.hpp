@@ -234,6 +234,14 @@ int launch_segm_rle_ragged(const float *masks, int M, int R, const float *boxes,
 int launch_rle_strings(const uint32_t *counts, const int32_t *ncounts, int M, int cap,
                        int32_t *lens, uint8_t *chars, hipStream_t s);
 
+// viz_mask_result's label maps (label_map.hip)
+size_t label_maps_workspace_bytes(int F, int cap);
+int launch_label_maps(const float *masks, int R, const float *dets, const int32_t *classes,
+                      const int32_t *counts, const uint8_t *valid, int F, int cap, int im_h,
+                      int im_w, float bin_thresh, float score_thresh, float gt_thresh,
+                      const uint8_t *lut, int lut_n, uint8_t *label, uint8_t *gt, void *workspace,
+                      size_t workspace_bytes, hipStream_t s);
+
 int launch_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                                  int box_stride, int min_size, float *out, hipStream_t s);
 int launch_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,

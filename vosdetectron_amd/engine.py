@@ -1118,6 +1118,26 @@ def frame_segms(pipe: FramePipeline, out: dict, num_classes: int = 81):
     return res
 
 
+def frame_label_maps(pipe: FramePipeline, out: dict, thresh: float = 0.25, gt_thresh=None,
+                     lut=None, valid=None):
+    """viz_mask_result's object-ID maps (lib/utils/vis.py:119-157) of every frame of a
+    step in one launch (ops.label_maps): -> (label, gt) uint8 device tensors
+    [F, H, W], gt None without gt_thresh (the reference's rvt_cls_threshold).  Serves
+    FramePipeline, VOSPipeline and C4FramePipeline outputs, completed or not: the
+    counts are read on the device, so a run(sync=False) output needs no complete()
+    first (detections past the padded mask batch -- exact score ties at
+    DETECTIONS_PER_IM -- are painted only after complete()).  valid [F, det_cap]
+    marks the rows a post-filter kept (VOSPipeline.frame_label_maps).  A
+    RaggedFramePipeline output is refused: its frames differ in size."""
+    if "frame_hw" in out or "im_hw" in out or isinstance(pipe, RaggedFramePipeline):
+        raise NotImplementedError("frame_label_maps: a RaggedFramePipeline step holds frames of "
+                                  "different sizes; label maps take one frame size per launch")
+    # complete() has checked the counts and trimmed the masks to their sum
+    return ops.label_maps(out["masks"], out["dets"], out["classes"], out["counts"], pipe.H,
+                          pipe.W, thresh, gt_thresh, pipe.cfg.MRCNN.THRESH_BINARIZE, lut, valid,
+                          rows_fit="counts_host" in out)
+
+
 def check_flow_args(flow, raw_flow, F, frame_hw, blob_hw, device):
     """VOSPipeline.run's flow arguments: at most one of flow (blob resolution) and
     raw_flow (F x H x W x 2 fp32 at frame resolution, on `device`); raw_flow needs
@@ -1271,6 +1291,30 @@ class VOSPipeline(FramePipeline):
                 cls_segms[j] = [rles[kept[i]] for i in rows]
             res.append((cls_boxes, cls_segms))
         return res
+
+    def frame_label_maps(self, out: dict, thresh: float = 0.25, gt_thresh=None, lut=None):
+        """frame_label_maps of a step's output showing exactly the detections
+        frame_results returns: with TEST.NMS_WITH_MASK_IOU > 0 the rows kept by the
+        mask-IoU NMS (which completes the step: it reads the counts) are passed as
+        `valid`.  Records nothing: the previous-frame state is frame_results' alone."""
+        tst = self.cfg.TEST
+        valid = None
+        if float(tst.NMS_WITH_MASK_IOU) > 0:
+            self.complete(out)
+            thr = self.cfg.MRCNN.THRESH_BINARIZE
+            valid = torch.zeros(tuple(out["classes"].shape), dtype=torch.uint8,
+                                device=self.device)
+            start = 0
+            for f, k in enumerate(int(k) for k in out["counts_host"]):
+                if k:
+                    dets, masks = out["dets"][f, :k], out["masks"][start:start + k]
+                    planes = ops.paste_masks(masks, dets, self.H, self.W, thr)
+                    keep = ops.mask_iou_nms(planes, dets, out["classes"][f, :k],
+                                            float(tst.NMS_WITH_MASK_IOU),
+                                            int(tst.NUM_DET_PER_CLASS_POST))
+                    valid[f, keep] = 1
+                start += k
+        return frame_label_maps(self, out, thresh, gt_thresh, lut, valid)
 
     def backbone(self, frames):
         feats = super().backbone(frames)

@@ -1868,6 +1868,85 @@ def rle_strings(counts: torch.Tensor, n: torch.Tensor) -> list:
 
 
 # --------------------------------------------------------------------------- #
+# viz_mask_result: per-frame object-ID maps                                    #
+# --------------------------------------------------------------------------- #
+LABEL_MAX_CAP = 1024  # csrc/label_map.hip kLabelMaxCap
+
+
+def label_lut(lut) -> np.ndarray:
+    """A class -> written id table as the uint8 array vd_label_maps takes: 1-D, at
+    least one entry, integers in [0, 255].  ValueError otherwise.  Needs no device."""
+    a = lut.detach().cpu().numpy() if isinstance(lut, torch.Tensor) else np.asarray(lut)
+    if a.ndim != 1 or a.size < 1:
+        raise ValueError("lut must be 1-D with at least one entry, got shape %s"
+                         % (tuple(a.shape),))
+    if a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 255:
+        raise ValueError("lut must hold integers in [0, 255]")
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+def label_maps(masks: torch.Tensor, dets: torch.Tensor, classes: torch.Tensor,
+               counts: torch.Tensor, im_h: int, im_w: int, score_thresh: float,
+               gt_thresh: Optional[float] = None, bin_thresh: float = 0.5, lut=None, valid=None,
+               rows_fit: bool = False):
+    """viz_mask_result's maps of every frame in one call (vd_label_maps): masks [M,R,R]
+    fp32 class-selected probabilities, rows in (frame, detection) order; dets [F,cap,5],
+    classes [F,cap] int32, counts [F] int32 on the device (read there: no host read, so a
+    run(sync=False) output is a valid input); valid [F,cap] uint8 / bool or None; lut a
+    class -> id table (label_lut; a uint8 device tensor is used as it is) or None for the
+    class itself.  -> (label, gt) uint8
+    [F,im_h,im_w]: the id of the highest-scoring detection with score >= float32(
+    score_thresh) whose pasted mask covers the pixel (equal scores: the higher row), and
+    the same where that score > float32(gt_thresh); gt is None without gt_thresh.
+    Rows past M are not painted: the counts are cut to the rows masks holds, on the device
+    (a few small torch kernels), unless M >= F * cap or the caller knows that they fit
+    (rows_fit: masks holds sum(clamp(counts, 0, cap)) rows, e.g. a completed step)."""
+    lut_t = None
+    if isinstance(lut, torch.Tensor) and lut.is_cuda and lut.dtype == torch.uint8 and \
+            lut.dim() == 1 and lut.numel() >= 1:
+        lut_t = lut.contiguous()  # already on the device: no copy, capturable
+    elif lut is not None:
+        lut_t = label_lut(lut)
+    m = _need(masks, "masks")
+    d, c, n = _need(dets, "dets"), _need(classes, "classes", torch.int32), \
+        _need(counts, "counts", torch.int32)
+    if d.dim() != 3 or d.shape[2] != 5:
+        raise ValueError("dets must be F x cap x 5, got %s" % (tuple(d.shape),))
+    F, cap = d.shape[0], d.shape[1]
+    if tuple(c.shape) != (F, cap) or n.numel() != F:
+        raise ValueError("label_maps: dets %s classes %s counts %s"
+                         % (tuple(d.shape), tuple(c.shape), tuple(n.shape)))
+    if m.dim() != 3 or m.shape[1] != m.shape[2]:
+        raise ValueError("masks must be M x R x R, got %s" % (tuple(m.shape),))
+    M, R = m.shape[0], m.shape[2]
+    v = None
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (F, cap):
+            raise ValueError("valid must be an F x cap tensor")
+        v = _need(valid.to(torch.uint8), "valid", torch.uint8)
+    label = torch.empty((F, int(im_h), int(im_w)), dtype=torch.uint8, device=d.device)
+    gt = torch.empty_like(label) if gt_thresh is not None else None
+    if F == 0:
+        return label, gt
+    if M < F * cap and not rows_fit:  # the counts may sum past the mask rows: cut them at M
+        end = n.clamp(0, cap).cumsum(0)
+        n = (end.clamp(max=M) - (end - n.clamp(0, cap)).clamp(max=M)).to(torch.int32)
+    if isinstance(lut_t, np.ndarray):
+        lut_t = torch.from_numpy(lut_t).to(d.device)
+    ws = _ws(lib().vd_label_maps_workspace_size(F, cap), d.device)
+    check(lib().vd_label_maps(
+        m.data_ptr() if M else d.data_ptr(), R, d.data_ptr(), c.data_ptr(), n.data_ptr(),
+        v.data_ptr() if v is not None else None, F, cap, int(im_h), int(im_w),
+        float(np.float32(bin_thresh)), float(np.float32(score_thresh)),
+        float(np.float32(gt_thresh if gt_thresh is not None else 0.0)),
+        lut_t.data_ptr() if lut_t is not None else None,
+        lut_t.numel() if lut_t is not None else 0,
+        label.data_ptr(), gt.data_ptr() if gt is not None else None, ws.data_ptr(), ws.numel(),
+        _stream()), "vd_label_maps")
+    return label, gt
+
+
+# --------------------------------------------------------------------------- #
 # keypoint_results: heatmap decode                                             #
 # --------------------------------------------------------------------------- #
 KEYPOINT_MAX_HEATMAP = 64  # csrc/keypoints.hip kKpMaxM
