@@ -914,6 +914,61 @@ int vd_label_maps(const float *masks, int R, const float *dets, const int32_t *c
                   size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * nms_with_mask_iou (lib_vos/tools/vos_test.py:985-1029) for every frame of a
+ * step in one call, without the H x W planes and without a host read.
+ *
+ * vd_mask_iou_nms_frames: masks / dets / classes / counts as vd_label_maps takes
+ * them -- masks `rows` rows of R x R fp32 in (frame, detection) order, the row of
+ * detection (f, i) being sum(clamp(counts[0..f), 0, cap)) + i, formed on the
+ * device; dets F x cap x 5 fp32, classes F x cap int32, counts F int32 (device).
+ * A count above cap is clamped, and the counts are cut to the rows masks holds:
+ * frame f takes the detections whose row is below `rows`.  Nothing outside the
+ * buffers is read or written whatever counts holds.
+ *
+ * Per frame the result is, bit for bit, vd_paste_masks (at bin_thresh) followed
+ * by vd_mask_iou_nms (iou_th, max_per_class) on the frame's detections: score
+ * order is np.argsort(-score) read stably (equal scores: the lower row first); a
+ * later position j is discarded by an earlier kept i when inter / (|m_i| + 1e-6)
+ * or inter / (|m_j| + 1e-6), in float64, is > iou_th; the kept rows are counted
+ * per class in score order and a class keeps its first max_per_class (0 keeps
+ * nothing); the output order is class ascending, then score order.
+ *   keep         F x cap int32: keep[f][0 .. keep_counts[f]) the kept rows i of
+ *                frame f in output order; entries past the count are untouched
+ *   keep_counts  F int32
+ *   valid        F x cap u8 or NULL: 1 on kept rows, 0 on the other rows below the
+ *                (cut) count, untouched past it
+ *   prev_dets (F x prev_cap x 5), prev_classes (F x prev_cap), prev_counts (F):
+ *                all three or none (VD_ERR_ARG otherwise); prev_cap >= cap.  The
+ *                kept dets / classes rows in keep order and their number: the
+ *                frame's final result as the next frame's previous result
+ *                (vd_detections_prev_box_filter).  Rows past the count untouched.
+ * A frame whose count is negative (a failure code of an upstream kernel) keeps
+ * that code in keep_counts[f], gets prev_counts[f] = 0 and no other write:
+ * propagate, never hide.
+ *
+ * Workspace: vd_mask_iou_nms_frames_workspace_size(F, cap, rows, im_h, im_w) bytes
+ * (0 for a shape the kernels refuse), 16-byte aligned, any contents:
+ *   rows * im_h * ceil(im_w / 64) * 8   the packed masks, 64 pixels per word on
+ *                                       the frame's 64-column grid
+ * + F * cap * cap * 4                   the pair intersections
+ * + rows * 20 + F * 8                   boxes, areas, first rows and cut counts
+ * each term rounded up to 256 bytes.  No term grows with rows * im_h * im_w bytes.
+ *
+ * R in 1..62, 1 <= cap <= 1024, 1 <= F <= 65535, im_h, im_w >= 1 with
+ * im_h * im_w < 2^31, prev_cap >= cap (VD_ERR_SHAPE otherwise); a workspace below
+ * the size gives VD_ERR_WORKSPACE; NULL masks / dets / classes / counts / keep /
+ * keep_counts / workspace, rows < 0 or one or two of the prev_* pointers give
+ * VD_ERR_ARG.  Nothing is launched on an error.  F == 0 returns VD_OK.
+ * ------------------------------------------------------------------------- */
+size_t vd_mask_iou_nms_frames_workspace_size(int F, int cap, int rows, int im_h, int im_w);
+int vd_mask_iou_nms_frames(const float *masks, int rows, int R, const float *dets,
+                           const int32_t *classes, const int32_t *counts, int F, int cap,
+                           int im_h, int im_w, float bin_thresh, double iou_th, int max_per_class,
+                           int32_t *keep, int32_t *keep_counts, uint8_t *valid, float *prev_dets,
+                           int32_t *prev_classes, int32_t *prev_counts, int prev_cap,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * keypoint_results' heatmap decode (lib/utils/keypoints.py:103-157
  * heatmaps_to_keypoints with scores_to_probs :214-222; called from
  * lib/core/test.py:858-874) on the device.

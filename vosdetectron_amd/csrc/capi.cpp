@@ -757,6 +757,27 @@ int vd_label_maps(const float *masks, int R, const float *dets, const int32_t *c
                              workspace, workspace_bytes, VD_STREAM(stream));
 }
 
+size_t vd_mask_iou_nms_frames_workspace_size(int F, int cap, int rows, int im_h, int im_w) {
+    return mask_iou_nms_frames_workspace_bytes(F, cap, rows, im_h, im_w);
+}
+
+int vd_mask_iou_nms_frames(const float *masks, int rows, int R, const float *dets,
+                           const int32_t *classes, const int32_t *counts, int F, int cap,
+                           int im_h, int im_w, float bin_thresh, double iou_th, int max_per_class,
+                           int32_t *keep, int32_t *keep_counts, uint8_t *valid, float *prev_dets,
+                           int32_t *prev_classes, int32_t *prev_counts, int prev_cap,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    if (F == 0) return VD_OK;
+    const int nprev = (prev_dets != nullptr) + (prev_classes != nullptr) + (prev_counts != nullptr);
+    if (!masks || !dets || !classes || !counts || !keep || !keep_counts || !workspace || F < 0 ||
+        rows < 0 || (nprev != 0 && nprev != 3))
+        return VD_ERR_ARG;
+    return launch_mask_iou_nms_frames(masks, rows, R, dets, classes, counts, F, cap, im_h, im_w,
+                                      bin_thresh, iou_th, max_per_class, keep, keep_counts, valid,
+                                      prev_dets, prev_classes, prev_counts, prev_cap, workspace,
+                                      workspace_bytes, VD_STREAM(stream));
+}
+
 int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                              int box_stride, int min_size, float *out, void *stream) {
     if (R == 0) return VD_OK;

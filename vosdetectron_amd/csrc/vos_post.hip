@@ -17,13 +17,12 @@
 // intersections are popcounts over the rows both masks occupy, and the greedy
 // pass runs in one workgroup with the discard flags in LDS.
 #include "common.hpp"
+#include "mask_nms_greedy.hpp"
 #include "vosdet_internal.hpp"
 
 namespace vd {
 
 namespace {
-
-constexpr int kMaxMaskNms = 1024;
 
 __global__ void zero_count_kernel(int32_t *p) { *p = 0; }
 
@@ -134,60 +133,12 @@ __global__ __launch_bounds__(1024) void mask_nms_kernel(int n, const float *__re
     __shared__ int order[kMaxMaskNms];   // position -> detection
     __shared__ int disc[kMaxMaskNms];    // by position
     __shared__ int sel[kMaxMaskNms];     // by position: kept and under the class cap
-    const int t = threadIdx.x;
-    // np.argsort(-scores), read stably: rank = #{k: s_k > s_t or (s_k == s_t, k < t)}
-    for (int d = t; d < n; d += blockDim.x) {
-        const float s = dets[(int64_t)d * stride + 4];
-        int rank = 0;
-        for (int k = 0; k < n; ++k) {
-            const float sk = dets[(int64_t)k * stride + 4];
-            rank += (sk > s) || (sk == s && k < d);
-        }
-        order[rank] = d;
-    }
-    for (int q = t; q < n; q += blockDim.x) disc[q] = 0;
-    __syncthreads();
-    for (int p = 0; p < n; ++p) {
-        if (!disc[p]) {  // uniform: read after the barrier
-            const int i = order[p];
-            const double ai = (double)ws.area[i] + 1e-6;
-            for (int q = p + 1 + t; q < n; q += blockDim.x) {
-                const int j = order[q];
-                const int inter = ws.inter[(int64_t)min(i, j) * n + max(i, j)];
-                const double iou1 = (double)inter / ai;
-                const double iou2 = (double)inter / ((double)ws.area[j] + 1e-6);
-                if (iou1 > iou_th || iou2 > iou_th) disc[q] = 1;
-            }
-        }
-        __syncthreads();
-    }
-    // the per-class cap in score order over the kept positions
-    for (int q = t; q < n; q += blockDim.x) {
-        int ok = 0;
-        if (!disc[q]) {
-            const int c = classes[order[q]];
-            int before = 0;
-            for (int u = 0; u < q; ++u) before += !disc[u] && classes[order[u]] == c;
-            ok = before < max_per_class;
-        }
-        sel[q] = ok;
-    }
-    __syncthreads();
-    // class-major output: class ascending, then score order
-    int nsel = 0;
-    for (int q = t; q < n; q += blockDim.x) {
-        if (!sel[q]) continue;
-        const int c = classes[order[q]];
-        int pos = 0;
-        for (int u = 0; u < n; ++u) {
-            if (!sel[u]) continue;
-            const int cu = classes[order[u]];
-            pos += cu < c || (cu == c && u < q);
-        }
-        keep_out[pos] = order[q];
-    }
-    for (int q = 0; q < n; ++q) nsel += sel[q];
-    if (t == 0) *num_out = nsel;
+    const int nsel = mask_nms_greedy(
+        n, [&](int d) { return dets[(int64_t)d * stride + 4]; },
+        [&](int d) { return classes[d]; }, [&](int d) { return ws.area[d]; },
+        [&](int i, int j) { return ws.inter[(int64_t)i * n + j]; }, iou_th, max_per_class, order,
+        disc, sel, [&](int pos, int d) { keep_out[pos] = d; });
+    if (threadIdx.x == 0) *num_out = nsel;
 }
 
 // box rows as float32, bb_intersection_over_union's expression order

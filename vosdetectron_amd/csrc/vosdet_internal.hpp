@@ -242,6 +242,16 @@ int launch_label_maps(const float *masks, int R, const float *dets, const int32_
                       const uint8_t *lut, int lut_n, uint8_t *label, uint8_t *gt, void *workspace,
                       size_t workspace_bytes, hipStream_t s);
 
+// nms_with_mask_iou over all frames of a step (mask_nms_frames.hip)
+size_t mask_iou_nms_frames_workspace_bytes(int F, int cap, int rows, int im_h, int im_w);
+int launch_mask_iou_nms_frames(const float *masks, int rows, int R, const float *dets,
+                               const int32_t *classes, const int32_t *counts, int F, int cap,
+                               int im_h, int im_w, float bin_thresh, double iou_th,
+                               int max_per_class, int32_t *keep, int32_t *keep_counts,
+                               uint8_t *valid, float *prev_dets, int32_t *prev_classes,
+                               int32_t *prev_counts, int prev_cap, void *workspace,
+                               size_t workspace_bytes, hipStream_t s);
+
 int launch_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                                  int box_stride, int min_size, float *out, hipStream_t s);
 int launch_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,

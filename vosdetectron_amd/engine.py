@@ -1205,8 +1205,8 @@ class VOSPipeline(FramePipeline):
         self.prev_dets = torch.zeros((F, det_cap, 5), dtype=torch.float32, device=self.device)
         self.prev_classes = torch.zeros((F, det_cap), dtype=torch.int32, device=self.device)
         self.prev_counts = torch.zeros((F,), dtype=torch.int32, device=self.device)
-        # a step whose result frame_results has not yet recorded as the previous
-        # frame (only tracked while a heuristic reads the previous result)
+        # a step whose result frame_results / finalize has not yet recorded as the
+        # previous frame (only tracked while a heuristic reads the previous result)
         self._unfinalized = False
 
     def heuristics_on(self) -> bool:
@@ -1248,41 +1248,68 @@ class VOSPipeline(FramePipeline):
                                            tst.NMS_SMALL_BOX_IOU,
                                            tst.NMS_SMALL_BOX_SCORE_THRESHOLD)
 
+    def finalize(self, out: dict) -> dict:
+        """The device-only tail of a step: the mask-IoU NMS of every row and the
+        record of each row's final result as the previous frame of its sequence
+        (prev_cls_boxes, for NMS_SMALL_BOX_IOU), with no host read and no complete():
+        after run(sync=False) + finalize(out) the next step can be queued.  With
+        TEST.NMS_WITH_MASK_IOU > 0 one ops.mask_iou_nms_frames call over all rows;
+        otherwise every row below its count is kept, in row order.  Stores
+        out["keep"] [F,det_cap] int32 (row f's kept detections in the reference's
+        output order), out["keep_counts"] [F] int32 and out["valid"] [F,det_cap]
+        uint8.  A second call on the same out does nothing."""
+        if "keep_counts" in out:
+            return out
+        tst = self.cfg.TEST
+        dets, classes, counts = out["dets"], out["classes"], out["counts"]
+        F, cap = dets.shape[0], dets.shape[1]
+        prev = (self.prev_dets[:F], self.prev_classes[:F], self.prev_counts[:F])
+        if float(tst.NMS_WITH_MASK_IOU) > 0:
+            keep, keep_counts, valid = ops.mask_iou_nms_frames(
+                out["masks"], dets, classes, counts, self.H, self.W,
+                float(tst.NMS_WITH_MASK_IOU), int(tst.NUM_DET_PER_CLASS_POST),
+                self.cfg.MRCNN.THRESH_BINARIZE, prev=prev, rows_fit="counts_host" in out)
+            out["_finalize_rows"] = out["masks"].shape[0]
+        else:
+            idx = torch.arange(cap, dtype=torch.int32, device=dets.device)
+            keep = idx.expand(F, cap).contiguous()
+            keep_counts = counts.clone()
+            valid = (idx[None, :] < counts[:, None]).to(torch.uint8)
+            prev[0].copy_(dets)
+            prev[1].copy_(classes)
+            prev[2].copy_(counts.clamp(0, cap))
+        out["keep"], out["keep_counts"], out["valid"] = keep, keep_counts, valid
+        self._unfinalized = False
+        return out
+
     def frame_results(self, out: dict, num_classes: int = None):
         """The tail of the VOS im_detect_all (lib_vos/tools/vos_test.py:50-120) for
         every row of a completed step: segm_results, then nms_with_mask_iou when
-        TEST.NMS_WITH_MASK_IOU > 0 (:113-118: masks pasted on the device, the mask
-        IoU NMS and the per-class cap of NUM_DET_PER_CLASS_POST on the device).
+        TEST.NMS_WITH_MASK_IOU > 0 (:113-118: finalize()'s one device call over all
+        rows, with the per-class cap of NUM_DET_PER_CLASS_POST).
         Returns a list over rows of (cls_boxes, cls_segms) -- cls_boxes[j] an
-        [n_j, 5] float32 array -- and records each row's result as the previous
-        frame of its sequence (prev_cls_boxes, for NMS_SMALL_BOX_IOU)."""
+        [n_j, 5] float32 array -- and, unless finalize() already has, records each
+        row's result as the previous frame of its sequence (prev_cls_boxes, for
+        NMS_SMALL_BOX_IOU)."""
         from . import segm
         K = num_classes or int(self.cfg.MODEL.NUM_CLASSES)
-        tst = self.cfg.TEST
         self.complete(out)
-        self._unfinalized = False
+        self._check_finalize_rows(out)
+        self.finalize(out)
         ks = [int(k) for k in out["counts_host"]]
         thr = self.cfg.MRCNN.THRESH_BINARIZE
+        keep_h = out["keep"].cpu().numpy()
+        nkeep = out["keep_counts"].cpu().tolist()
+        dets_h, classes_h = out["dets"].cpu().numpy(), out["classes"].cpu().numpy()
         res, start = [], 0
-        mask_nms = float(tst.NMS_WITH_MASK_IOU) > 0
         for f, k in enumerate(ks):
             dets = out["dets"][f, :k]
-            classes = out["classes"][f, :k]
             masks = out["masks"][start:start + k]
             start += k
             rles = segm.encode_masks(masks, dets, self.H, self.W, thr)
-            keep = torch.arange(k, device=self.device)
-            if mask_nms and k:
-                planes = ops.paste_masks(masks, dets, self.H, self.W, thr)
-                keep = ops.mask_iou_nms(planes, dets, classes, float(tst.NMS_WITH_MASK_IOU),
-                                        int(tst.NUM_DET_PER_CLASS_POST))
-            kd, kc = dets[keep], classes[keep]
-            n = kd.shape[0]
-            self.prev_dets[f, :n] = kd
-            self.prev_classes[f, :n] = kc
-            self.prev_counts[f] = n
-            kd_h, kc_h = kd.cpu().numpy(), kc.cpu().tolist()
-            kept = keep.cpu().tolist()
+            kept = keep_h[f, :nkeep[f]].astype(np.int64)
+            kd_h, kc_h = dets_h[f][kept], classes_h[f][kept].tolist()
+            kept = kept.tolist()
             cls_boxes = [np.zeros((0, 5), np.float32) for _ in range(K)]
             cls_segms = [[] for _ in range(K)]
             for j in sorted(set(kc_h)):
@@ -1292,28 +1319,24 @@ class VOSPipeline(FramePipeline):
             res.append((cls_boxes, cls_segms))
         return res
 
+    @staticmethod
+    def _check_finalize_rows(out):
+        """A finalize() before complete() saw the padded mask batch; if complete() then
+        added rows (exact score ties at DETECTIONS_PER_IM), its NMS missed them."""
+        rows = out.get("_finalize_rows")
+        if rows is not None and sum(out["counts_host"]) > rows:
+            raise RuntimeError("VOSPipeline.finalize ran on %d mask rows but the step holds %d "
+                               "detections (score ties at DETECTIONS_PER_IM): complete() the "
+                               "step before finalize()" % (rows, sum(out["counts_host"])))
+
     def frame_label_maps(self, out: dict, thresh: float = 0.25, gt_thresh=None, lut=None):
         """frame_label_maps of a step's output showing exactly the detections
         frame_results returns: with TEST.NMS_WITH_MASK_IOU > 0 the rows kept by the
-        mask-IoU NMS (which completes the step: it reads the counts) are passed as
-        `valid`.  Records nothing: the previous-frame state is frame_results' alone."""
-        tst = self.cfg.TEST
+        mask-IoU NMS (finalize(), run here if it has not: no host read, no complete())
+        are passed as `valid`."""
         valid = None
-        if float(tst.NMS_WITH_MASK_IOU) > 0:
-            self.complete(out)
-            thr = self.cfg.MRCNN.THRESH_BINARIZE
-            valid = torch.zeros(tuple(out["classes"].shape), dtype=torch.uint8,
-                                device=self.device)
-            start = 0
-            for f, k in enumerate(int(k) for k in out["counts_host"]):
-                if k:
-                    dets, masks = out["dets"][f, :k], out["masks"][start:start + k]
-                    planes = ops.paste_masks(masks, dets, self.H, self.W, thr)
-                    keep = ops.mask_iou_nms(planes, dets, out["classes"][f, :k],
-                                            float(tst.NMS_WITH_MASK_IOU),
-                                            int(tst.NUM_DET_PER_CLASS_POST))
-                    valid[f, keep] = 1
-                start += k
+        if float(self.cfg.TEST.NMS_WITH_MASK_IOU) > 0:
+            valid = self.finalize(out)["valid"]
         return frame_label_maps(self, out, thresh, gt_thresh, lut, valid)
 
     def backbone(self, frames):
@@ -1344,13 +1367,14 @@ class VOSPipeline(FramePipeline):
         resized, scaled, padded and brought to the five levels in one launch;
         sync as FramePipeline.run (False: complete() reads the counts later).
         With TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU on, every step's result
-        must pass through frame_results before the next step runs (the filter
-        reads the previous frame's final result): raises otherwise."""
+        must pass through frame_results or finalize before the next step runs (the
+        filter reads the previous frame's final result): raises otherwise."""
         if self._unfinalized and self.heuristics_on():
             raise RuntimeError(
                 "VOSPipeline.run: the previous step's result has not been through "
-                "frame_results(); TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU need it as the "
-                "next frame's previous result (lib_vos/tools/vos_test.py:113-118, 845-860)")
+                "frame_results() or finalize(); TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU need "
+                "it as the next frame's previous result (lib_vos/tools/vos_test.py:113-118, "
+                "845-860)")
         if self.delta_flow:
             check_delta_flow_args(flow, raw_flow, (self.Hp, self.Wp))
         check_flow_args(flow, raw_flow, int(frames.shape[0]), (self.H, self.W), (self.Hp, self.Wp),

@@ -1657,6 +1657,80 @@ def mask_iou_nms(planes: torch.Tensor, dets: torch.Tensor, classes: torch.Tensor
     return keep[: int(num.item())]
 
 
+def mask_iou_nms_frames_workspace(F: int, cap: int, rows: int, im_h: int, im_w: int) -> int:
+    """Bytes of workspace vd_mask_iou_nms_frames takes for this shape (0: refused)."""
+    return int(lib().vd_mask_iou_nms_frames_workspace_size(int(F), int(cap), int(rows),
+                                                           int(im_h), int(im_w)))
+
+
+def mask_iou_nms_frames(masks: torch.Tensor, dets: torch.Tensor, classes: torch.Tensor,
+                        counts: torch.Tensor, im_h: int, im_w: int, iou_th: float,
+                        max_per_class: int, bin_thresh: float = 0.5, prev=None,
+                        want_valid: bool = True, rows_fit: bool = False,
+                        workspace_budget: int = 1 << 30):
+    """nms_with_mask_iou (lib_vos/tools/vos_test.py:985-1029) of every frame of a step
+    in one call (vd_mask_iou_nms_frames), from the R x R mask probabilities: masks
+    [M,R,R] fp32 class-selected, rows in (frame, detection) order; dets [F,cap,5],
+    classes [F,cap] int32, counts [F] int32 on the device, as label_maps takes them.
+    Nothing is read on the host and no allocation depends on a device value, so counts
+    still being computed on the stream are a valid input and the call can be captured.
+    -> (keep [F,cap] int32, keep_counts [F] int32, valid [F,cap] uint8 or None):
+    keep[f, :keep_counts[f]] are frame f's kept rows in the reference's output order
+    (class ascending, then score order), exactly what paste_masks + mask_iou_nms give
+    on that frame; valid marks them.  A negative count stays in keep_counts.
+    prev = (prev_dets [F,pcap,5], prev_classes [F,pcap] int32, prev_counts [F] int32),
+    pcap >= cap, contiguous: receives the kept rows and their number in place (the
+    previous-frame result detections_prev_box_filter reads).  Detections whose mask row
+    is past M are cut on the device; rows_fit (the caller knows they fit) changes
+    nothing here and is accepted for symmetry with label_maps.  ValueError when the
+    workspace exceeds workspace_budget bytes."""
+    m = _need(masks, "masks")
+    d, c, n = _need(dets, "dets"), _need(classes, "classes", torch.int32), \
+        _need(counts, "counts", torch.int32)
+    if d.dim() != 3 or d.shape[2] != 5:
+        raise ValueError("dets must be F x cap x 5, got %s" % (tuple(d.shape),))
+    F, cap = d.shape[0], d.shape[1]
+    if tuple(c.shape) != (F, cap) or n.numel() != F:
+        raise ValueError("mask_iou_nms_frames: dets %s classes %s counts %s"
+                         % (tuple(d.shape), tuple(c.shape), tuple(n.shape)))
+    if m.dim() != 3 or m.shape[1] != m.shape[2]:
+        raise ValueError("masks must be M x R x R, got %s" % (tuple(m.shape),))
+    M, R = m.shape[0], m.shape[2]
+    pd = pc = pn = None
+    pcap = 0
+    if prev is not None:
+        pd, pc, pn = prev
+        for t, name, dt in ((pd, "prev_dets", torch.float32), (pc, "prev_classes", torch.int32),
+                            (pn, "prev_counts", torch.int32)):
+            if _need(t, name, dt) is not t:
+                raise ValueError("%s must be contiguous: it is written in place" % name)
+        pcap = pd.shape[1] if pd.dim() == 3 else 0
+        if pd.dim() != 3 or pd.shape[0] != F or pd.shape[2] != 5 or pcap < cap or \
+                tuple(pc.shape) != (F, pcap) or pn.numel() != F:
+            raise ValueError("prev must be ([F,pcap,5], [F,pcap], [F]) with F = %d and "
+                             "pcap >= cap = %d" % (F, cap))
+    keep = torch.zeros((F, cap), dtype=torch.int32, device=d.device)
+    keep_counts = torch.zeros((F,), dtype=torch.int32, device=d.device)
+    valid = torch.zeros((F, cap), dtype=torch.uint8, device=d.device) if want_valid else None
+    if F == 0:
+        return keep, keep_counts, valid
+    size = mask_iou_nms_frames_workspace(F, cap, M, im_h, im_w)
+    if size > int(workspace_budget):
+        raise ValueError("mask_iou_nms_frames: the workspace for F = %d, cap = %d, %d mask rows "
+                         "at %d x %d is %d bytes, above workspace_budget = %d"
+                         % (F, cap, M, im_h, im_w, size, int(workspace_budget)))
+    ws = _ws(size, d.device)
+    check(lib().vd_mask_iou_nms_frames(
+        m.data_ptr() if M else d.data_ptr(), M, R, d.data_ptr(), c.data_ptr(), n.data_ptr(), F,
+        cap, int(im_h), int(im_w), float(np.float32(bin_thresh)), float(iou_th),
+        int(max_per_class), keep.data_ptr(), keep_counts.data_ptr(),
+        valid.data_ptr() if valid is not None else None,
+        pd.data_ptr() if pd is not None else None, pc.data_ptr() if pc is not None else None,
+        pn.data_ptr() if pn is not None else None, pcap, ws.data_ptr(), ws.numel(), _stream()),
+        "vd_mask_iou_nms_frames")
+    return keep, keep_counts, valid
+
+
 # --------------------------------------------------------------------------- #
 # segm_results: paste + binarize + RLE counts (SURVEY.md section 8f row 3)      #
 # --------------------------------------------------------------------------- #
