@@ -969,6 +969,58 @@ int vd_mask_iou_nms_frames(const float *masks, int rows, int R, const float *det
                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * im_detect_bbox on caller-given boxes (MODEL.FASTER_RCNN False; lib/core/test.py
+ * :128-190, lib_vos/tools/vos_test.py:137-205), the part before the heads, for every
+ * frame of a step in one call: _get_rois_blob (test.py:877-906) and the DEDUP_BOXES
+ * hash with np.unique (test.py:132-139).
+ *
+ * vd_rois_from_boxes: boxes F x cap x 4 fp32 in image coordinates, counts F int32
+ * (device), im_scale F float64 (get_target_scale's scalar per frame), dedup
+ * cfg.DEDUP_BOXES as float32.  Per frame f with n = counts[f] rows:
+ *   RoI of row r   (f, float32(float64(box) * im_scale[f])): column 0 is the frame
+ *   hash           np.round(roi * dedup) in float32 (half to even), then the float64
+ *                  dot with (1, 1e3, 1e6, 1e9, 1e12); exact for blobs < 16000 pixels
+ *   np.unique      the distinct hashes ascending; index = the first row of each,
+ *                  inv_index = the position of each row's hash.  Two boxes that round
+ *                  to one hash are merged onto the first, as the reference merges them
+ *   rois      F x cap x 5 fp32   rois[f][u] = the RoI of row index[f][u], u < ucounts[f]
+ *   ucounts   F int32            the number of distinct hashes
+ *   index     F x cap int32      u < ucounts[f]
+ *   inv_index F x cap int32      r < counts[f]
+ * Rows past ucounts[f] in rois / index and past counts[f] in inv_index are not
+ * written.  dedup == 0 is the identity: index = inv_index = 0 .. n - 1, the RoIs in
+ * input order, ucounts = counts.  counts[f] == 0 writes ucounts[f] = 0 and nothing
+ * else; counts[f] > cap writes ucounts[f] = VD_COUNT_SELECT_FAILED and nothing else;
+ * a negative count (an upstream failure code) is copied to ucounts[f].
+ *
+ * No allocation, host copy or synchronisation: the call can be captured.  The keys
+ * are sorted in LDS, so vd_rois_from_boxes_workspace(F, cap) is 0 and workspace may
+ * be NULL; the pair is kept so that a larger capacity need not change the interface.
+ * 1 <= cap <= 4096 and F >= 1 (VD_ERR_SHAPE otherwise); a NULL pointer, F < 0 or a
+ * dedup that is negative or NaN give VD_ERR_ARG.  F == 0 returns VD_OK.
+ *
+ * vd_gather_rows: test.py:186-189 (scores[inv_index], pred_boxes[inv_index]) moved in
+ * front of the decode, which is a function of the row alone.  For r < counts[f], with
+ * u = inv_index[f][r]: scores_out[f][r] = scores[f][u] (F x cap x K), deltas_out[f][r] =
+ * deltas[f][u] (F x cap x D), and rows_out[f][r] = (f, boxes[f][index[f][u]]), the
+ * caller's own box of the representative (boxes[index], test.py:139): the reference
+ * decodes from it, not from RoI / im_scale, so vd_box_detections takes rows_out as its
+ * rois with an im_scale of 1.  Rows past counts[f] are not written.  counts_out[f] =
+ * counts[f], or ucounts[f] when that is negative (the frame failed; nothing else is
+ * written for it): the roi_count vd_box_detections takes.  An inv_index entry outside
+ * [0, ucounts[f]) or an index entry outside [0, counts[f]) leaves its row unwritten.
+ * F <= 65535, cap <= 4096, K, D >= 1 (VD_ERR_SHAPE otherwise).
+ * ------------------------------------------------------------------------- */
+size_t vd_rois_from_boxes_workspace(int F, int cap);
+int vd_rois_from_boxes(const float *boxes, const int32_t *counts, const double *im_scale,
+                       float dedup, int F, int cap, float *rois, int32_t *ucounts, int32_t *index,
+                       int32_t *inv_index, void *workspace, size_t workspace_bytes, void *stream);
+int vd_gather_rows(const float *boxes, const float *scores, const float *deltas,
+                   const int32_t *index, const int32_t *inv_index, const int32_t *counts,
+                   const int32_t *ucounts, int F, int cap, int K, int D, float *rows_out,
+                   float *scores_out, float *deltas_out, int32_t *counts_out, void *stream);
+
+/* ---------------------------------------------------------------------------
  * keypoint_results' heatmap decode (lib/utils/keypoints.py:103-157
  * heatmaps_to_keypoints with scores_to_probs :214-222; called from
  * lib/core/test.py:858-874) on the device.

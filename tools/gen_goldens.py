@@ -23,12 +23,17 @@ Runtime-only import shims (nothing under /root/reference is modified):
     never called on the functions used here; vos_post.npz's mask-IoU NMS gets a
     decode / encode stub that carries binary masks, see gen_vos_post_fixture);
   * ``np.delete`` accepting an integral float64 index array (vos_test.py:1011,
-    what numpy of the reference's era did), for vos_post.npz only.
+    what numpy of the reference's era did), for vos_post.npz only;
+  * for given_boxes.npz only: ``cv2.resize`` returning zeros of the resized shape (the
+    blob's pixels are never read by the stand-in model) and ``np.unique`` wrapped by a
+    recorder that returns what numpy returns (index / inv_index are locals of
+    im_detect_bbox).
 
 Usage: python tools/gen_goldens.py   (writes tests/golden/*.npz)
        python tools/gen_goldens.py vos_post   (only tests/golden/vos_post.npz)
        python tools/gen_goldens.py soft_nms   (only tests/golden/soft_nms.npz)
        python tools/gen_goldens.py nms_oks    (only tests/golden/nms_oks.npz)
+       python tools/gen_goldens.py given_boxes   (only tests/golden/given_boxes.npz)
        python tools/gen_goldens.py conv3x3_routes   (only tests/golden/conv3x3_routes.json:
                                                this checkout's own route decisions)
 """
@@ -784,9 +789,116 @@ def gen_conv3x3_routes_fixture():
         os.path.getsize(path), len(codes)))
 
 
+def gen_given_boxes_fixture():
+    """tests/golden/given_boxes.npz: the reference's own im_detect_bbox
+    (lib/core/test.py:128-190) executed with MODEL.FASTER_RCNN False on caller-given
+    boxes, for FPN (FPN.MULTILEVEL_ROIS) and single-level settings.
+
+    The model is a stand-in (tests/given_boxes_ref.standin_head): cls_score and bbox_pred
+    are fixed float32 functions of the RoI rows it is handed, so scores and pred_boxes pin
+    which rows the head saw and in what order; it also records its inputs (rois, the
+    per-level RoIs, the restore index).  cv2 is absent: cv2.resize, the one third-party
+    step of get_image_blob, is a stub that returns zeros of the resized shape -- the
+    blob's pixels are never read; get_target_scale, _get_rois_blob, the hash, np.unique,
+    _add_multilevel_rois_for_test, bbox_transform, clip_tiled_boxes and the inverse map
+    are the reference's code.  Cases: tests/given_boxes_ref.case_boxes."""
+    install_shims()
+    import torch
+    from core.config import cfg
+    import core.test as ref_test
+    import cv2
+    from tests import given_boxes_ref as gb
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    from gen_label_map_goldens import save_npz
+
+    def _resize(im, dsize, dst, fx, fy, interpolation):
+        return np.zeros((int(round(im.shape[0] * fy)), int(round(im.shape[1] * fx)),
+                         im.shape[2]), np.float32)
+    cv2.resize = _resize
+    _np_unique = np.unique
+    seen = {}
+
+    class _StandIn:
+        def __call__(self, data, im_info, rois, **levels):
+            assert isinstance(rois, np.ndarray) and rois.dtype == np.float32
+            seen.clear()
+            seen["rois"] = rois.copy()
+            for k, v in levels.items():
+                seen[k] = np.array(v, copy=True)
+            scores, deltas = gb.standin_head(rois)
+            return {"cls_score": torch.from_numpy(scores), "bbox_pred": torch.from_numpy(deltas),
+                    "blob_conv": None}
+
+    cfg.MODEL.FASTER_RCNN = False
+    cfg.MODEL.NUM_CLASSES = gb.K
+    cfg.MODEL.BBOX_REG_WEIGHTS = gb.REG_WEIGHTS
+    cfg.TEST.BBOX_REG = True
+    assert not cfg.MODEL.CLS_AGNOSTIC_BBOX_REG
+    assert not cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED
+    out = {}
+    merged = 0
+    for fpn in (True, False):
+        cfg.FPN.FPN_ON = fpn
+        cfg.FPN.MULTILEVEL_ROIS = fpn
+        tag = "fpn" if fpn else "single"
+        for name, (boxes, im_shape, (scale, max_size), dd) in gb.case_boxes().items():
+            cfg.DEDUP_BOXES = dd
+            im = np.zeros(im_shape, np.uint8)
+            given = boxes.copy()
+            calls = []
+            np.unique = lambda *a, **k: calls.append(_np_unique(*a, **k)) or calls[-1]
+            try:
+                scores, pred_boxes, im_scale, _ = ref_test.im_detect_bbox(
+                    _StandIn(), im, scale, max_size, boxes=given)
+            finally:
+                np.unique = _np_unique
+            assert np.array_equal(given, boxes)
+            (im_scale,) = im_scale
+            n, u = len(boxes), len(seen["rois"])
+            assert scores.shape == (n, gb.K) and pred_boxes.shape == (n, 4 * gb.K)
+            assert scores.dtype == np.float32 and pred_boxes.dtype == np.float32
+            # index / inv_index are locals of im_detect_bbox: np.unique is wrapped by a
+            # recorder for the call.  Cross-check against what the head saw and returned
+            head_scores, _ = gb.standin_head(seen["rois"])
+            blob = gb.rois_blob(boxes, im_scale)
+            if dd > 0:
+                (_, index, inv), = calls
+                inv = inv.reshape(-1)
+                assert len(np.unique(head_scores, axis=0)) == u
+                assert np.array_equal(seen["rois"], blob[index])
+                assert np.array_equal(scores, head_scores[inv])
+            else:  # no de-dup: the head saw every row, in the caller's order
+                assert not calls
+                assert np.array_equal(seen["rois"], blob)
+                assert np.array_equal(scores, head_scores)
+                index = inv = np.arange(n)
+            merged += n - u
+            pre = "%s/%s/" % (tag, name)
+            out[pre + "boxes"] = boxes
+            out[pre + "im_shape"] = np.array(im_shape, np.int64)
+            out[pre + "im_scale"] = np.float64(im_scale)
+            out[pre + "dedup"] = np.float64(dd)
+            out[pre + "index"] = index.astype(np.int64)
+            out[pre + "inv_index"] = inv.astype(np.int64)
+            out[pre + "scores"] = scores
+            out[pre + "pred_boxes"] = pred_boxes
+            for k, v in seen.items():
+                out[pre + k] = v
+            assert fpn == ("rois_idx_restore_int32" in seen)
+    assert merged > 0
+    os.makedirs(OUT, exist_ok=True)
+    path = os.path.join(OUT, "given_boxes.npz")
+    save_npz(path, **out)
+    size = os.path.getsize(path)
+    assert size <= 1 << 20, size
+    print("wrote %s (%d bytes): %d arrays, %d rows merged" % (path, size, len(out), merged))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["conv3x3_routes"]:
         gen_conv3x3_routes_fixture()
+    elif sys.argv[1:] == ["given_boxes"]:
+        gen_given_boxes_fixture()
     elif sys.argv[1:] == ["vos_post"]:
         gen_vos_post_fixture()
     elif sys.argv[1:] == ["soft_nms"]:
@@ -798,3 +910,4 @@ if __name__ == "__main__":
         gen_vos_post_fixture()
         gen_soft_nms_fixture()
         gen_nms_oks_fixture()
+        gen_given_boxes_fixture()

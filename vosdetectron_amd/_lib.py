@@ -162,6 +162,10 @@ SIGNATURES = {
     "vd_mask_iou_nms_frames_workspace_size": (_S, [_I, _I, _I, _I, _I]),
     "vd_mask_iou_nms_frames": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, ctypes.c_double,
                                     _I, _P, _P, _P, _P, _P, _P, _I, _P, _S, _P]),
+    # im_detect_bbox on given boxes: RoI blob + DEDUP_BOXES, and the gather back
+    "vd_rois_from_boxes_workspace": (_S, [_I, _I]),
+    "vd_rois_from_boxes": (_I, [_P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _S, _P]),
+    "vd_gather_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     # keypoint_results (heatmap decode)
     "vd_heatmaps_to_keypoints": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     # im_detect_keypoints_aug's combination fused into the decode

@@ -81,3 +81,33 @@ def box_voting(top_dets, all_dets, thresh, scoring_method="ID", beta=1.0):
     if t.shape[0] == 0:
         return t.copy()
     return ops.box_voting(_dev(t), _dev(all_dets), thresh, scoring_method, beta).cpu().numpy()
+
+
+def dedup_boxes(rois, dedup=0.0625):
+    """The DEDUP_BOXES step of im_detect_bbox (lib/core/test.py:132-139) on the device
+    (vd_rois_from_boxes): rois an (N, 5) float32 ndarray (column 0 the level, 0 in the
+    reference's RoI blob, the box already at the blob's scale) -> (rois[index], index,
+    inv_index) as np.unique(hashes, return_index=True, return_inverse=True) gives them:
+    the distinct hashes ascending, each by its first row.  dedup == 0 returns the rows
+    unchanged with index = inv_index = arange(N).  A restriction against the reference's
+    lines: column 0 must be 0 in every row, which is all _get_rois_blob ever writes; the
+    kernel takes that column from the frame a row belongs to, so another value raises
+    ValueError instead of being hashed."""
+    r = np.ascontiguousarray(rois, np.float32)
+    if r.ndim != 2 or r.shape[1] != 5:
+        raise ValueError("rois must be N x 5, got %s" % (r.shape,))
+    N = r.shape[0]
+    if N == 0:
+        return r.copy(), np.zeros((0,), np.int64), np.zeros((0,), np.int64)
+    if np.any(r[:, 0] != 0):
+        raise ValueError("dedup_boxes: column 0 (the blob level) must be 0, as _get_rois_blob "
+                         "writes it")
+    if N > ops.GIVEN_BOXES_CAP:
+        raise ValueError("dedup_boxes: %d rows exceed %d per call" % (N, ops.GIVEN_BOXES_CAP))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out, ucounts, index, inv_index = ops.rois_from_boxes(
+        _dev(r[:, 1:5]).view(1, N, 4), torch.full((1,), N, dtype=torch.int32, device=dev),
+        torch.ones((1,), dtype=torch.float64, device=dev), dedup)
+    u = int(ucounts.item())
+    return (out[0, :u].cpu().numpy(), index[0, :u].cpu().numpy().astype(np.int64),
+            inv_index[0, :N].cpu().numpy().astype(np.int64))

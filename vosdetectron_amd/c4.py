@@ -206,6 +206,7 @@ class C4FramePipeline(FramePipeline):
       14x14 masks.
     """
     ASYNC = False  # run() always reads the counts (the C4 mask batch is host-sized)
+    GIVEN_BOXES = False
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
                  det_cap=256, device="cuda"):

@@ -101,6 +101,12 @@ def default_cfg() -> AttrDict:
             # (NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU below are built: VOSPipeline)
             NMS_WITH_MASK_IOU=0., NMS_SMALL_BOX_IOU=0.,  # config.py:951-953: the VOS
             NMS_SMALL_BOX_SCORE_THRESHOLD=0.),  # loop's heuristics (engine.VOSPipeline)
+        # config.py:86-96: read at inference by im_detect_bbox (lib/core/test.py:174-177);
+        # refused when on (UNSUPPORTED), the other TRAIN keys stay out of scope
+        TRAIN=_d(BBOX_NORMALIZE_TARGETS_PRECOMPUTED=False),
+        # config.py:1004: the hash quantum of im_detect_bbox on caller-given boxes
+        # (MODEL.FASTER_RCNN False, lib/core/test.py:132-139); 0 switches the de-dup off
+        DEDUP_BOXES=1 / 16.,
         PIXEL_MEANS=(102.9801, 115.9465, 122.7717),  # config.py:1015
         BBOX_XFORM_CLIP=math.log(1000. / 16.),  # config.py:1009
         CROP_RESIZE_WITH_MAX_POOL=True,  # config.py:1058
@@ -169,6 +175,9 @@ UNSUPPORTED = (
     ("TEST.KPS_AUG.ENABLED", bool, "keypoint test-time augmentation, lib/core/test.py:567-730, "
      "as a config key: load_cfg(..., test_aug=True) accepts it on a MODEL.KEYPOINTS_ON config "
      "for engine.KeypointAugFramePipeline"),
+    ("TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED", bool,
+     "legacy de-normalisation of the box deltas by precomputed means and stds, "
+     "lib/core/test.py:174-177"),
     ("MODEL.USE_DELTA_FLOW", _WithCfg(lambda v, c: bool(v) and not c.get("VOS", False)),
      "delta-flow head on a model other than Generalized_VOS_RCNN: only the VOS builder has it, "
      "lib_vos/vos_modeling/vos_model_builder.py:95-104"),

@@ -778,6 +778,35 @@ int vd_mask_iou_nms_frames(const float *masks, int rows, int R, const float *det
                                       workspace_bytes, VD_STREAM(stream));
 }
 
+size_t vd_rois_from_boxes_workspace(int F, int cap) {
+    return rois_from_boxes_workspace_bytes(F, cap);
+}
+
+int vd_rois_from_boxes(const float *boxes, const int32_t *counts, const double *im_scale,
+                       float dedup, int F, int cap, float *rois, int32_t *ucounts, int32_t *index,
+                       int32_t *inv_index, void *workspace, size_t workspace_bytes, void *stream) {
+    if (F == 0) return VD_OK;
+    if (!boxes || !counts || !im_scale || !rois || !ucounts || !index || !inv_index || F < 0 ||
+        !(dedup >= 0.f))
+        return VD_ERR_ARG;
+    (void)workspace;  // vd_rois_from_boxes_workspace is 0: nothing to carve
+    (void)workspace_bytes;
+    return launch_rois_from_boxes(boxes, counts, im_scale, dedup, F, cap, rois, ucounts, index,
+                                  inv_index, VD_STREAM(stream));
+}
+
+int vd_gather_rows(const float *boxes, const float *scores, const float *deltas,
+                   const int32_t *index, const int32_t *inv_index, const int32_t *counts,
+                   const int32_t *ucounts, int F, int cap, int K, int D, float *rows_out,
+                   float *scores_out, float *deltas_out, int32_t *counts_out, void *stream) {
+    if (F == 0) return VD_OK;
+    if (!boxes || !scores || !deltas || !index || !inv_index || !counts || !ucounts ||
+        !rows_out || !scores_out || !deltas_out || !counts_out || F < 0)
+        return VD_ERR_ARG;
+    return launch_gather_rows(boxes, scores, deltas, index, inv_index, counts, ucounts, F, cap, K,
+                              D, rows_out, scores_out, deltas_out, counts_out, VD_STREAM(stream));
+}
+
 int vd_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                              int box_stride, int min_size, float *out, void *stream) {
     if (R == 0) return VD_OK;

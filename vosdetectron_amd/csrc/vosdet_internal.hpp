@@ -252,6 +252,18 @@ int launch_mask_iou_nms_frames(const float *masks, int rows, int R, const float 
                                int32_t *prev_counts, int prev_cap, void *workspace,
                                size_t workspace_bytes, hipStream_t s);
 
+// im_detect_bbox on caller-given boxes: RoI blob + DEDUP_BOXES, and the gather back
+// (given_boxes.hip)
+constexpr int kGivenBoxesCap = 4096;  // rows per frame: the sort keys fill 48 KiB of LDS
+size_t rois_from_boxes_workspace_bytes(int F, int cap);
+int launch_rois_from_boxes(const float *boxes, const int32_t *counts, const double *im_scale,
+                           float dedup, int F, int cap, float *rois, int32_t *ucounts,
+                           int32_t *index, int32_t *inv_index, hipStream_t s);
+int launch_gather_rows(const float *boxes, const float *scores, const float *deltas,
+                       const int32_t *index, const int32_t *inv_index, const int32_t *counts,
+                       const int32_t *ucounts, int F, int cap, int K, int D, float *rows_out,
+                       float *scores_out, float *deltas_out, int32_t *counts_out, hipStream_t s);
+
 int launch_heatmaps_to_keypoints(const float *maps, int R, int K, int M, const float *boxes,
                                  int box_stride, int min_size, float *out, hipStream_t s);
 int launch_heatmaps_to_keypoints_aug(const float *const *view_maps, int V, uint32_t hflip_mask,

@@ -146,6 +146,9 @@ def view_dets(dets, g):
     return _flip_dets(dets, g.flip_w) if g.hflip else dets
 
 
+GIVEN_BOXES_STEP_CAP = 2048  # csrc/detections.hip kDetRMax: RoI rows per frame of a step
+
+
 class FramePipeline:
     """The step every pipeline here runs (_run): the box pass (_box_pass: body, box
     stages, detections; leaves each head view's geometry and pyramid in out["_pyrs"]),
@@ -154,6 +157,7 @@ class FramePipeline:
     ASYNC = True  # run(sync=False) queues a step with no host read (see run())
     KEYPOINTS = False  # the class runs the MODEL.KEYPOINTS_ON configs
     TEST_AUG = ()  # which of TEST.BBOX_AUG / MASK_AUG / KPS_AUG the class serves
+    GIVEN_BOXES = True  # the class runs MODEL.FASTER_RCNN False: run(box_proposals=...)
     mask_heur = None  # one mask view, no combination
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
@@ -189,6 +193,16 @@ class FramePipeline:
             raise NotImplementedError(
                 "%s: TEST.KPS_AUG runs on KeypointAugFramePipeline (FPN keypoint configs, "
                 "frames of one size)" % name)
+        self.given_boxes = not cfg.MODEL.FASTER_RCNN
+        if self.given_boxes and not self.GIVEN_BOXES:
+            raise NotImplementedError(
+                "%s: MODEL.FASTER_RCNN False (detection from the caller's box_proposals, "
+                "lib/core/test.py:128-190) runs on FramePipeline and VOSPipeline; ragged, C4, "
+                "augmented and keypoint steps with given boxes are not built" % name)
+        if self.given_boxes and cfg.get("TRAIN", {}).get("BBOX_NORMALIZE_TARGETS_PRECOMPUTED"):
+            raise NotImplementedError(
+                "%s: TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED (lib/core/test.py:174-177) is not "
+                "built" % name)
         if not cfg.MODEL.KEYPOINTS_ON and not hasattr(model, "Mask_Head"):
             raise NotImplementedError(
                 "%s: the model has no Mask_Head (MODEL.MASK_ON False); a box-only step is "
@@ -199,6 +213,7 @@ class FramePipeline:
         self.device = torch.device(device)
         self.channels_last = channels_last
         self.det_cap = det_cap
+        self._proposals = None  # the step's box_proposals while run() is inside _run
         self._nms_options = nms_options(cfg)
         # the views whose pyramids the heads read: here the identity view alone
         self.head_views = [(tst.SCALE, tst.MAX_SIZE, False)]
@@ -206,8 +221,8 @@ class FramePipeline:
         if cfg.FPN.FPN_ON:
             k_min, k_max = cfg.FPN.RPN_MIN_LEVEL, cfg.FPN.RPN_MAX_LEVEL
             self.rpn_levels = list(range(k_min, k_max + 1))
-            self.anchors = [getattr(model, "anchors_fpn%d" % l).to(self.device)
-                            for l in self.rpn_levels]
+            self.anchors = [] if self.given_boxes else [
+                getattr(model, "anchors_fpn%d" % l).to(self.device) for l in self.rpn_levels]
             self.rpn_scales = [1. / 2 ** l for l in self.rpn_levels]
             self.roi_levels = list(range(cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL + 1))
             self.roi_scales = [1. / 2 ** l for l in self.roi_levels]
@@ -278,7 +293,8 @@ class FramePipeline:
         return out
 
     @torch.no_grad()
-    def run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
+    def run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True,
+            box_proposals=None):
         """frames: F x H x W x 3 uint8 BGR on the device.  Returns a dict of device
         tensors: dets [F,cap,5] (x1,y1,x2,y2,score), classes [F,cap], counts [F],
         masks [M,28,28] for the M = sum(counts) detections in (frame, class,
@@ -286,15 +302,61 @@ class FramePipeline:
         any host read (graph-capturable): masks then has mask_rows(F) rows of
         which the first M are real, and complete(out) later reads the counts and
         trims.  Stage marks (enable_timers): conv_body, proposals, box_head
-        (together the reference's im_detect_bbox), misc_bbox, im_detect_mask."""
+        (together the reference's im_detect_bbox), misc_bbox, im_detect_mask.
+        box_proposals = (boxes [F,cap,4] fp32 in frame coordinates, counts [F] int32), on
+        the device: required with MODEL.FASTER_RCNN False, where the heads run on the
+        caller's boxes (im_detect_all(model, im, box_proposals), lib/core/test.py:56-107):
+        the RoIs are de-duplicated at cfg.DEDUP_BOXES (ops.rois_from_boxes), the box head
+        sees each distinct RoI once, and every given row takes its RoI's scores and
+        decoded box (ops.gather_rows) into box_results_with_nms_and_limit.  out["rois"] /
+        ["roi_counts"] / ["cls_prob"] / ["bbox_pred"] are then the distinct RoIs and the
+        head's outputs on them, out["box_index"] / ["box_inv_index"] the two maps, and
+        out["det_rois"] / ["det_cls_prob"] / ["det_bbox_pred"] / ["det_roi_counts"] the
+        rows the detections were made from.  ValueError with MODEL.FASTER_RCNN True,
+        where the reference ignores them."""
+        self._proposals = self._check_box_proposals(box_proposals, frames)
         if self.timers is not None:
             self._marks = []
             self._mark("start")
         try:
             return self._run(frames, keep_intermediates, sync)
         finally:
+            self._proposals = None
             if self.timers is not None:
                 self._collect_marks()
+
+    def _check_box_proposals(self, box_proposals, frames):
+        name = type(self).__name__
+        if box_proposals is not None and not self.GIVEN_BOXES:
+            raise NotImplementedError(
+                "%s.run: box_proposals (detection from given boxes) run on FramePipeline and "
+                "VOSPipeline; ragged, C4, augmented and keypoint steps with given boxes are "
+                "not built" % name)
+        if not self.given_boxes:
+            if box_proposals is not None:
+                raise ValueError(
+                    "%s.run: box_proposals with MODEL.FASTER_RCNN True: the boxes come from "
+                    "the RPN and the reference ignores the caller's (lib/core/test.py:128-160); "
+                    "build the model and the pipeline with MODEL.FASTER_RCNN False" % name)
+            return None
+        if box_proposals is None:
+            raise ValueError("%s.run: MODEL.FASTER_RCNN False needs box_proposals = (boxes "
+                             "[F,cap,4] float32, counts [F] int32) on the device" % name)
+        boxes, counts = box_proposals
+        F = int(frames.shape[0])
+        for t, what, dt in ((boxes, "boxes", torch.float32), (counts, "counts", torch.int32)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+                raise ValueError("%s.run: box_proposals %s must be a device tensor of %s"
+                                 % (name, what, dt))
+        if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4 \
+                or tuple(counts.shape) != (F,):
+            raise ValueError("%s.run: box_proposals must be ([F,cap,4], [F]) with F = %d, got "
+                             "%s and %s" % (name, F, tuple(boxes.shape), tuple(counts.shape)))
+        if not 1 <= boxes.shape[1] <= GIVEN_BOXES_STEP_CAP:
+            raise ValueError("%s.run: box_proposals hold cap = %d rows per frame, outside 1..%d "
+                             "(vd_box_detections' RoI capacity)"
+                             % (name, boxes.shape[1], GIVEN_BOXES_STEP_CAP))
+        return boxes.contiguous(), counts.contiguous()
 
     def _run(self, frames: torch.Tensor, keep_intermediates: bool = False, sync: bool = True):
         out = self._box_pass(frames, keep_intermediates)
@@ -311,19 +373,35 @@ class FramePipeline:
         g = self._frame_rows(frames)
         feats = self.backbone(frames)
         self._mark("conv_body")
-        rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post = \
-            self._box_stages(feats, g.im_info)
+        if self.given_boxes:
+            stages, index, inv_index = self._given_box_stages(feats, g)
+        else:
+            stages = self._box_stages(feats, g.im_info)
+        rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post = stages
         F, K = g.F, cls_prob.shape[1]
+        det_in = (rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt)
+        det_scale = g.im_scale_t
+        if self.given_boxes:
+            # every given row takes its RoI's scores and deltas and the caller's box of
+            # that RoI, which the reference decodes from (boxes[index], test.py:139, :178):
+            # the detections read the box rows as RoIs at scale 1
+            boxes, counts = self._proposals
+            det_in = ops.gather_rows(boxes, det_in[1], det_in[2], index, inv_index, counts,
+                                     rcnt)
+            det_scale = torch.ones((F,), dtype=torch.float32, device=self.device)
         dets, dcls, dcnt = ops.box_detections(
-            rois, cls_prob.view(F, post, K), bbox_pred.view(F, post, 4 * K), rcnt,
-            g.im_scale_t, g.im_hw, tst.SCORE_THRESH, tst.NMS,
-            tst.DETECTIONS_PER_IM, cfg.MODEL.BBOX_REG_WEIGHTS, self.det_cap,
+            *det_in, det_scale, g.im_hw, tst.SCORE_THRESH,
+            tst.NMS, tst.DETECTIONS_PER_IM, cfg.MODEL.BBOX_REG_WEIGHTS, self.det_cap,
             nms_cross_class=tst.NMS_CROSS_CLASS, num_det_per_class_pre=tst.NUM_DET_PER_CLASS_PRE,
             **self._nms_options)
         self._post_detections(dets, dcls, dcnt)
         self._mark("misc_bbox")
         out = {"dets": dets, "classes": dcls, "counts": dcnt, "rois": rois, "roi_counts": rcnt,
                "cls_prob": cls_prob, "bbox_pred": bbox_pred}
+        if self.given_boxes:
+            out.update(box_index=index, box_inv_index=inv_index, det_rois=det_in[0],
+                       det_cls_prob=det_in[1], det_bbox_pred=det_in[2],
+                       det_roi_counts=det_in[3])
         if keep_intermediates:  # for stage-wise parity tests
             out.update(feats=feats, rpn_probs=probs, rpn_deltas=deltas, pyramid=pyr)
         # the pyramid stays referenced only until complete() (the rare overflow batch
@@ -356,9 +434,15 @@ class FramePipeline:
         rois, rlvl, rcnt = ops.collect_distribute(lrois, lprobs, lcnt, post,
                                                   cfg.FPN.ROI_MIN_LEVEL, cfg.FPN.ROI_MAX_LEVEL)
         self._mark("proposals")
+        pyr, fast, cls_prob, bbox_pred = self._box_head(feats, rois.view(-1, 5), rlvl.view(-1))
+        return rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post
+
+    def _box_head(self, feats, flat_rois, flat_lvl):
+        """Box RoIAlign over the NHWC pyramid and the box head on flat_rois [R,5] at
+        levels flat_lvl (level - ROI_MIN_LEVEL) -> (pyramid, fast, cls_prob, the per-class
+        bbox_pred)."""
         pyr = self.nhwc_pyramid(feats)
-        fr = cfg.FAST_RCNN
-        flat_rois, flat_lvl = rois.view(-1, 5), rlvl.view(-1)
+        fr = self.cfg.FAST_RCNN
         fast = self._nhwc_heads()
         box_feat = ops.roi_align_fpn(pyr, self.roi_scales, flat_rois, flat_lvl,
                                      fr.ROI_XFORM_RESOLUTION, fr.ROI_XFORM_SAMPLING_RATIO,
@@ -368,7 +452,28 @@ class FramePipeline:
         cls_prob, bbox_pred = self.model.Box_Outs(x)
         self._mark("box_head")
         bbox_pred = self.model.Box_Outs.per_class_deltas(bbox_pred, cls_prob.shape[1])
-        return rois, rcnt, cls_prob, bbox_pred, probs, deltas, pyr, fast, post
+        return pyr, fast, cls_prob, bbox_pred
+
+    def _given_box_stages(self, feats, g):
+        """_box_stages with MODEL.FASTER_RCNN False (lib/core/test.py:128-154): no RPN
+        heads, proposals or collect; the step's box_proposals become the distinct RoIs of
+        every frame in one call (_get_rois_blob + DEDUP_BOXES, ops.rois_from_boxes), which
+        get their FPN levels (_add_multilevel_rois_for_test) and go through the box head.
+        -> (_box_stages' tuple, index, inv_index); the RoI counts are the numbers of distinct
+        RoIs.  Rows past them are zero boxes on frame 0 whose outputs nothing reads."""
+        cfg, fpn = self.cfg, self.cfg.FPN
+        boxes, counts = self._proposals
+        rois, ucnt, index, inv_index = ops.rois_from_boxes(
+            boxes, counts, g.im_scale_d, cfg.get("DEDUP_BOXES", 1 / 16.))
+        flat_rois = rois.view(-1, 5)
+        flat_lvl = ops.map_rois_to_fpn_levels(flat_rois, fpn.ROI_MIN_LEVEL, fpn.ROI_MAX_LEVEL,
+                                              canonical_scale=fpn.ROI_CANONICAL_SCALE,
+                                              canonical_level=fpn.ROI_CANONICAL_LEVEL)
+        flat_lvl.sub_(fpn.ROI_MIN_LEVEL)  # the index into the RoI levels roi_align_fpn takes
+        self._mark("proposals")
+        pyr, fast, cls_prob, bbox_pred = self._box_head(feats, flat_rois, flat_lvl)
+        return (rois, ucnt, cls_prob, bbox_pred, [], [], pyr, fast, boxes.shape[1]), index, \
+            inv_index
 
     def _post_detections(self, dets, classes, counts):
         """Hook after box_results_with_nms_and_limit's device steps (the VOS loop
@@ -491,6 +596,12 @@ class FramePipeline:
         Idempotent."""
         if "counts_host" in out:
             return out
+        if "box_inv_index" in out:  # given boxes: a frame whose count exceeded cap
+            over = [f for f, c in enumerate(out["roi_counts"].cpu().tolist()) if c < 0]
+            if over:
+                raise ops._lib.VosdetError("box_proposals: the counts of frame(s) %s exceed the "
+                                       "cap of %d rows per frame (or are negative)"
+                                       % (over, out["box_inv_index"].shape[1]))
         counts = out["counts"].cpu().tolist()
         self._check_counts(counts)
         keys = ("masks", "mask_rois", "mask_feat")
@@ -530,6 +641,7 @@ class KeypointFramePipeline(FramePipeline):
     kps_boxes stay in pre-NMS row order; keep_intermediates adds dets_pre_oks,
     classes_pre_oks, counts_pre_oks and keyps_pre_oks.  Stage mark: misc_oks_nms."""
     KEYPOINTS = True
+    GIVEN_BOXES = False
     BOXES_FIRST = True  # _keypoints: the decode's boxes are queued ahead of the head
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
@@ -832,6 +944,7 @@ class AugFramePipeline(_AugViews, FramePipeline):
     and mask_rois, masks (mask views), and out["cand_counts"] [F,K]."""
 
     TEST_AUG = ("BBOX_AUG", "MASK_AUG")
+    GIVEN_BOXES = False
     box_union = True  # one box view too goes through the union
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
@@ -881,6 +994,7 @@ class KeypointAugFramePipeline(_AugViews, KeypointFramePipeline):
     im_detect_keypoints, misc_keypoints, misc_oks_nms."""
 
     TEST_AUG = ("BBOX_AUG", "KPS_AUG")
+    GIVEN_BOXES = False
     BOXES_FIRST = False
 
     def __init__(self, model, cfg, frame_hw=(800, 1333), batch=1, channels_last=False,
@@ -1013,6 +1127,7 @@ class RaggedFramePipeline(FramePipeline):
 
     All per-frame geometry lives in a RaggedBatch on the device and no frame size
     is a launch argument, so one captured step replays with other sizes."""
+    GIVEN_BOXES = False
 
     def __init__(self, model, cfg, blob_hw, batch=1, capacity_bytes=None, channels_last=False,
                  det_cap=256, device="cuda"):
@@ -1045,7 +1160,8 @@ class RaggedFramePipeline(FramePipeline):
         return batch  # it carries the per-frame rows itself
 
     @torch.no_grad()
-    def run(self, batch: RaggedBatch, keep_intermediates: bool = False, sync: bool = True):
+    def run(self, batch: RaggedBatch, keep_intermediates: bool = False, sync: bool = True,
+            box_proposals=None):
         """batch: a loaded RaggedBatch of this pipeline (new_batch().load(frames)).
         Returns FramePipeline.run's dict plus im_hw, the batch's [F, 2] device rows;
         sync=False makes no host read and is graph-capturable.  complete() adds
@@ -1055,6 +1171,8 @@ class RaggedFramePipeline(FramePipeline):
             raise ValueError("run() takes a RaggedBatch made by this pipeline's new_batch()")
         if batch.sizes is None:
             raise ValueError("the batch is empty: load() frames first")
+        if box_proposals is not None:  # NotImplementedError by name, before batch.shape
+            self._check_box_proposals(box_proposals, batch)
         return super().run(batch, keep_intermediates, sync)
 
     def _run(self, batch, keep_intermediates=False, sync=True):
@@ -1359,13 +1477,16 @@ class VOSPipeline(FramePipeline):
 
     @torch.no_grad()
     def run(self, frames: torch.Tensor, flow: torch.Tensor = None, raw_flow: torch.Tensor = None,
-            keep_intermediates=False, sync: bool = True):
+            keep_intermediates=False, sync: bool = True, box_proposals=None):
         """frames: F x H x W x 3 u8 (frame t of each sequence); flow: optional
         F x 2 x Hp x Wp optical flow at blob resolution (flo_to_blob, data_flow);
         raw_flow: instead of flow, the F x H x W x 2 fp32 flow as read from the .flo
         files (flow_io.read_flo) at the pipeline's frame_hw, on the device -- it is
         resized, scaled, padded and brought to the five levels in one launch;
-        sync as FramePipeline.run (False: complete() reads the counts later).
+        sync and box_proposals as FramePipeline.run (sync False: complete() reads the
+        counts later; box_proposals with MODEL.FASTER_RCNN False: the heads run on the
+        caller's boxes, such as the previous step's kept rows that finalize() leaves on
+        the device).
         With TEST.NMS_WITH_MASK_IOU / NMS_SMALL_BOX_IOU on, every step's result
         must pass through frame_results or finalize before the next step runs (the
         filter reads the previous frame's final result): raises otherwise."""
@@ -1381,7 +1502,8 @@ class VOSPipeline(FramePipeline):
                         self.device)
         self._flow, self._raw_flow = flow, raw_flow
         try:
-            out = super().run(frames, keep_intermediates, sync=sync)
+            out = super().run(frames, keep_intermediates, sync=sync,
+                              box_proposals=box_proposals)
         finally:
             self._flow = self._raw_flow = None
         self._unfinalized = True

@@ -1357,7 +1357,11 @@ class Generalized_RCNN(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.Conv_Body = FPNBody(cfg)
-        self.RPN = FPNRPNOutputs(self.Conv_Body.dim_out, len(cfg.FPN.RPN_ASPECT_RATIOS))
+        # model_builder.py:83: cfg.RPN.RPN_ON is MODEL.FASTER_RCNN (or RPN_ONLY); a Fast
+        # R-CNN model has no RPN modules and takes its boxes from the caller
+        self.rpn_on = bool(cfg.MODEL.FASTER_RCNN)
+        if self.rpn_on:
+            self.RPN = FPNRPNOutputs(self.Conv_Body.dim_out, len(cfg.FPN.RPN_ASPECT_RATIOS))
         self.num_roi_levels = cfg.FPN.ROI_MAX_LEVEL - cfg.FPN.ROI_MIN_LEVEL + 1
         roi_scales = self.Conv_Body.spatial_scale[-self.num_roi_levels:]
         self.roi_spatial_scale = roi_scales  # coarsest first, as the reference
@@ -1378,7 +1382,7 @@ class Generalized_RCNN(nn.Module):
             self.Keypoint_Outs = KeypointOutputs(self.Keypoint_Head.dim_out, cfg)
         anchors = []
         k_min, k_max = cfg.FPN.RPN_MIN_LEVEL, cfg.FPN.RPN_MAX_LEVEL
-        for lvl in range(k_min, k_max + 1):
+        for lvl in range(k_min, k_max + 1 if self.rpn_on else k_min):
             anchors.append(torch.from_numpy(generate_anchors(
                 stride=2. ** lvl, sizes=(cfg.FPN.RPN_ANCHOR_START_SIZE * 2. ** (lvl - k_min),),
                 aspect_ratios=cfg.FPN.RPN_ASPECT_RATIOS)))
@@ -1432,7 +1436,8 @@ class Generalized_RCNN(nn.Module):
         the bias/residual/ReLU after each conv run as one vd_bias_act pass (GN
         bodies: each GroupNorm + residual + ReLU as one vd_group_norm_act)."""
         prepare_fpn_body(self.Conv_Body, epilogue)
-        self.RPN.fuse()
+        if self.rpn_on:
+            self.RPN.fuse()
         self.Box_Head.prepare()
         if hasattr(self, "Mask_Head"):
             self.Mask_Head.prepare()

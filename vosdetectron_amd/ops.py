@@ -1418,6 +1418,116 @@ def collect_distribute(level_rois, level_probs, level_counts, post_nms_topN: int
     return rois, lvl, cnt
 
 
+GIVEN_BOXES_CAP = 4096  # csrc/vosdet_internal.hpp kGivenBoxesCap
+
+
+def rois_from_boxes_workspace(F: int, cap: int) -> int:
+    """Bytes of workspace vd_rois_from_boxes takes (0: its keys live in LDS)."""
+    return int(lib().vd_rois_from_boxes_workspace(int(F), int(cap)))
+
+
+def rois_from_boxes(boxes: torch.Tensor, counts: torch.Tensor, im_scale: torch.Tensor,
+                    dedup: float = 0.0625, out=None):
+    """The front of im_detect_bbox for caller-given boxes (lib/core/test.py:128-139 with
+    MODEL.FASTER_RCNN False): _get_rois_blob and the DEDUP_BOXES hash + np.unique, for
+    every frame of a step in one call (vd_rois_from_boxes).  boxes [F,cap,4] fp32 in image
+    coordinates, counts [F] int32, im_scale [F] float64, all on the device; dedup is
+    cfg.DEDUP_BOXES (0: no de-dup).  Nothing is read on the host, so the call can be
+    captured.  -> (rois [F,cap,5], ucounts [F] int32, index [F,cap] int32, inv_index
+    [F,cap] int32): rois[f, :ucounts[f]] are frame f's distinct RoIs in ascending hash
+    order (column 0 = f), index their first rows, inv_index[f, :counts[f]] each row's RoI.
+    Rows past the counts keep what `out` held (zeros when allocated here).  A count above
+    cap leaves ucounts[f] = -1 (raise_on_failed_counts)."""
+    b = _need(boxes, "boxes")
+    n = _need(counts, "counts", torch.int32)
+    sc = _need(im_scale, "im_scale", torch.float64)
+    if b.dim() != 3 or b.shape[2] != 4:
+        raise ValueError("boxes must be F x cap x 4, got %s" % (tuple(b.shape),))
+    F, cap = b.shape[0], b.shape[1]
+    if n.numel() != F or sc.numel() != F:
+        raise ValueError("rois_from_boxes: boxes %s counts %s im_scale %s"
+                         % (tuple(b.shape), tuple(n.shape), tuple(sc.shape)))
+    if not 1 <= cap <= GIVEN_BOXES_CAP:
+        raise ValueError("rois_from_boxes: cap = %d is outside 1..%d rows per frame"
+                         % (cap, GIVEN_BOXES_CAP))
+    if not float(dedup) >= 0:
+        raise ValueError("rois_from_boxes: DEDUP_BOXES = %r is negative" % (dedup,))
+    if out is None:
+        rois = torch.zeros((F, cap, 5), dtype=torch.float32, device=b.device)
+        ucounts = torch.zeros((F,), dtype=torch.int32, device=b.device)
+        index = torch.zeros((F, cap), dtype=torch.int32, device=b.device)
+        inv_index = torch.zeros((F, cap), dtype=torch.int32, device=b.device)
+    else:
+        rois, ucounts, index, inv_index = out
+    if F:  # no workspace: rois_from_boxes_workspace is 0, the C entry takes NULL
+        check(lib().vd_rois_from_boxes(b.data_ptr(), n.data_ptr(), sc.data_ptr(),
+                                       float(np.float32(dedup)), F, cap, rois.data_ptr(),
+                                       ucounts.data_ptr(), index.data_ptr(),
+                                       inv_index.data_ptr(), None, 0, _stream()),
+              "vd_rois_from_boxes")
+    return rois, ucounts, index, inv_index
+
+
+def get_rois_blob(im_rois, im_scale, frame: int = 0) -> np.ndarray:
+    """_get_rois_blob (lib/core/test.py:877-890), an ndarray drop-in: R x 4 boxes in image
+    coordinates -> R x 5 float32 (frame, box * im_scale), through vd_rois_from_boxes
+    without the de-dup."""
+    b = np.ascontiguousarray(im_rois, dtype=np.float32).reshape(-1, 4)
+    R = b.shape[0]
+    if R == 0:
+        return np.zeros((0, 5), np.float32)
+    if R > GIVEN_BOXES_CAP:
+        raise ValueError("get_rois_blob: %d boxes exceed %d per call" % (R, GIVEN_BOXES_CAP))
+    dev = torch.device("cuda")
+    F = int(frame) + 1  # the kernel writes its frame number into column 0
+    boxes = torch.zeros((F, R, 4), dtype=torch.float32, device=dev)
+    boxes[frame] = torch.from_numpy(b).to(dev)
+    counts = torch.zeros((F,), dtype=torch.int32, device=dev)
+    counts[frame] = R
+    scale = torch.full((F,), float(np.asarray(im_scale, np.float64).reshape(-1)[0]),
+                       dtype=torch.float64, device=dev)
+    rois, _, _, _ = rois_from_boxes(boxes, counts, scale, 0.)
+    return rois[frame].cpu().numpy()
+
+
+def gather_rows(boxes: torch.Tensor, scores: torch.Tensor, deltas: torch.Tensor,
+                index: torch.Tensor, inv_index: torch.Tensor, counts: torch.Tensor,
+                ucounts: torch.Tensor, out=None):
+    """scores[inv_index], pred_boxes[inv_index] of im_detect_bbox (lib/core/test.py:186-189)
+    in front of the decode (vd_gather_rows): scores [F,cap,K] and deltas [F,cap,D] of the
+    distinct RoIs and the caller's boxes [F,cap,4] -> for the caller's rows r < counts[f]
+    the scores and deltas of row inv_index[f, r] and the box rows (f, boxes[f,
+    index[f, inv_index[f, r]]]) [F,cap,5] the reference decodes from (boxes[index],
+    test.py:139): box_detections takes them as its rois with an im_scale of 1.  The fourth
+    result is its roi_count: counts, or the failure code of ucounts.  Rows past counts
+    keep what `out` held (zeros here)."""
+    b, s, d = _need(boxes, "boxes"), _need(scores, "scores"), _need(deltas, "deltas")
+    i, v = _need(index, "index", torch.int32), _need(inv_index, "inv_index", torch.int32)
+    n, u = _need(counts, "counts", torch.int32), _need(ucounts, "ucounts", torch.int32)
+    if b.dim() != 3 or b.shape[2] != 4:
+        raise ValueError("boxes must be F x cap x 4, got %s" % (tuple(b.shape),))
+    F, cap = b.shape[0], b.shape[1]
+    if s.dim() != 3 or d.dim() != 3 or tuple(s.shape[:2]) != (F, cap) or \
+            tuple(d.shape[:2]) != (F, cap) or tuple(i.shape) != (F, cap) or \
+            tuple(v.shape) != (F, cap) or n.numel() != F or u.numel() != F:
+        raise ValueError("gather_rows: boxes %s scores %s deltas %s index %s inv_index %s "
+                         "counts %s ucounts %s"
+                         % (tuple(b.shape), tuple(s.shape), tuple(d.shape), tuple(i.shape),
+                            tuple(v.shape), tuple(n.shape), tuple(u.shape)))
+    if out is None:
+        ro = torch.zeros((F, cap, 5), dtype=torch.float32, device=b.device)
+        so, do = torch.zeros_like(s), torch.zeros_like(d)
+        co = torch.zeros((F,), dtype=torch.int32, device=b.device)
+    else:
+        ro, so, do, co = out
+    if F:
+        check(lib().vd_gather_rows(b.data_ptr(), s.data_ptr(), d.data_ptr(), i.data_ptr(),
+                                   v.data_ptr(), n.data_ptr(), u.data_ptr(), F, cap, s.shape[2],
+                                   d.shape[2], ro.data_ptr(), so.data_ptr(), do.data_ptr(),
+                                   co.data_ptr(), _stream()), "vd_gather_rows")
+    return ro, so, do, co
+
+
 SOFT_NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}  # utils/boxes.py:344
 BBOX_VOTE_METHODS = {"ID": 0, "AVG": 1, "IOU_AVG": 2, "QUASI_SUM": 3}
 

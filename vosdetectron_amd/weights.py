@@ -91,15 +91,17 @@ def calibrate(model, frame_u8: np.ndarray, device):
             hooks.append(t.conv_lateral.register_forward_hook(unit_out()))
         for p in body.posthoc_modules:
             hooks.append(p.register_forward_hook(unit_out()))
-    rpn = model.RPN
-    hooks.append(rpn.FPN_RPN_conv.register_forward_hook(unit_out()))
-    hooks.append(rpn.FPN_RPN_cls_score.register_forward_hook(unit_out(1.5, -1.5)))
-    hooks.append(rpn.FPN_RPN_bbox_pred.register_forward_hook(unit_out(0.2)))
+    rpn = getattr(model, "RPN", None)  # None: MODEL.FASTER_RCNN False, boxes are given
+    if rpn is not None:
+        hooks.append(rpn.FPN_RPN_conv.register_forward_hook(unit_out()))
+        hooks.append(rpn.FPN_RPN_cls_score.register_forward_hook(unit_out(1.5, -1.5)))
+        hooks.append(rpn.FPN_RPN_bbox_pred.register_forward_hook(unit_out(0.2)))
     feats = body(blob)
     if hasattr(model, "temporal_fusion"):  # VOS: the RPN sees the ConvGRU-fused pyramid
         feats = model.temporal_fusion(feats, fused=False)
         model.clean_hidden_states()
-    rpn.level_outputs(feats[-1])  # calibrate the shared RPN convs on P2
+    if rpn is not None:
+        rpn.level_outputs(feats[-1])  # calibrate the shared RPN convs on P2
     for h in hooks:
         h.remove()
     for m in model.modules():
@@ -173,7 +175,8 @@ def build_model(cfg, seed: int = 0, device="cuda", fold=True, channels_last=Fals
         m.fold_affine()
     if channels_last:
         m.Conv_Body.to(memory_format=torch.channels_last)
-        m.RPN.to(memory_format=torch.channels_last)
+        if hasattr(m, "RPN"):
+            m.RPN.to(memory_format=torch.channels_last)
         if c4:
             m.Box_Head.to(memory_format=torch.channels_last)
             m.Mask_Head.upconv5.to(memory_format=torch.channels_last)
