@@ -914,6 +914,52 @@ int vd_label_maps(const float *masks, int R, const float *dets, const int32_t *c
                   size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The DAVIS annotation file of every frame of a step: the last step of
+ * viz_mask_result (lib/utils/vis.py:152-155; img_saver is davis_saver ->
+ * io.imwrite_indexed, imdb/vos/davis_db.py:45-47), an 8-bit indexed PNG of the
+ * label map, formed on the device.
+ *
+ * vd_label_pngs: labels F x H x W u8 (vd_label_maps' label or gt), palette 256 x 3
+ * u8 RGB (device), out F x cap u8, lengths F int32.  out[f][0 .. lengths[f]) is a
+ * complete PNG file: signature; IHDR (W, H, bit depth 8, colour type 3, no
+ * interlace); PLTE with 256 entries; one IDAT holding a zlib stream (header 78 01);
+ * IEND.  Every chunk CRC-32 and the Adler-32 are computed on the device.  The
+ * decoded pixels equal labels[f], the decoded palette equals palette.  Bytes of
+ * out[f] past lengths[f] hold no defined value.  No host read, no device
+ * allocation: the call can be graph-captured.  The bytes depend on the inputs
+ * alone, not on what out or workspace held, and are the same in every run.
+ *
+ * Deflate form: filter type 0 on every row; rows in strips of 8; a strip is one
+ * fixed-Huffman block of literals and distance-1 matches of 3..258 bytes (runs
+ * within a row), and every strip but the last (BFINAL) is followed by an empty
+ * stored block, so that it ends on a byte boundary.
+ *
+ * vd_label_png_bound(H, W): the per-frame capacity no input can exceed, host only:
+ *     843                           signature 8, IHDR 25, PLTE 780, IDAT length and
+ *                                   type 8, zlib header 2, Adler-32 4, IDAT CRC 4,
+ *                                   IEND 12
+ *   + sum over strips of r rows of  floor((9 r (W + 1) + 20) / 8) + 4
+ * A strip is at most: 3 bits of block header, 9 bits (the longest literal) for each
+ * of its r (W + 1) filtered bytes -- a match costs at most 8 + 5 + 5 bits for at
+ * least 3 bytes, never more than the literals it replaces --, 7 bits of end of
+ * block, 3 bits of stored-block header, up to 7 bits of padding, 4 bytes LEN / NLEN.
+ * 0 for a size the kernel does not serve.  cap below the bound is refused
+ * (VD_ERR_ARG) before any launch, so there is no overflow at run time; the strips
+ * are first written at their worst-case offsets inside out[f] and then joined.
+ *
+ * 1 <= W <= 4095, 1 <= H <= 16384, F <= 65535 (VD_ERR_SHAPE otherwise);
+ * workspace_bytes >= vd_label_pngs_workspace(F, H, W) (VD_ERR_WORKSPACE; 16 bytes
+ * per strip; 0 for a shape the kernel refuses), 16-byte aligned, any contents; NULL
+ * labels / palette / out / lengths / workspace or cap < bound give VD_ERR_ARG.
+ * Nothing is launched on an error.  F == 0 returns VD_OK.
+ * ------------------------------------------------------------------------- */
+size_t vd_label_png_bound(int H, int W);
+size_t vd_label_pngs_workspace(int F, int H, int W);
+int vd_label_pngs(const uint8_t *labels, int F, int H, int W, const uint8_t *palette,
+                  uint8_t *out, size_t cap, int32_t *lengths, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * nms_with_mask_iou (lib_vos/tools/vos_test.py:985-1029) for every frame of a
  * step in one call, without the H x W planes and without a host read.
  *

@@ -757,6 +757,19 @@ int vd_label_maps(const float *masks, int R, const float *dets, const int32_t *c
                              workspace, workspace_bytes, VD_STREAM(stream));
 }
 
+size_t vd_label_png_bound(int H, int W) { return label_png_bound(H, W); }
+
+size_t vd_label_pngs_workspace(int F, int H, int W) { return label_pngs_workspace_bytes(F, H, W); }
+
+int vd_label_pngs(const uint8_t *labels, int F, int H, int W, const uint8_t *palette,
+                  uint8_t *out, size_t cap, int32_t *lengths, void *workspace,
+                  size_t workspace_bytes, void *stream) {
+    if (F == 0) return VD_OK;
+    if (!labels || !palette || !out || !lengths || F < 0) return VD_ERR_ARG;
+    return launch_label_pngs(labels, F, H, W, palette, out, cap, lengths, workspace,
+                             workspace_bytes, VD_STREAM(stream));
+}
+
 size_t vd_mask_iou_nms_frames_workspace_size(int F, int cap, int rows, int im_h, int im_w) {
     return mask_iou_nms_frames_workspace_bytes(F, cap, rows, im_h, im_w);
 }

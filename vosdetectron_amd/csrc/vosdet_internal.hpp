@@ -242,6 +242,13 @@ int launch_label_maps(const float *masks, int R, const float *dets, const int32_
                       const uint8_t *lut, int lut_n, uint8_t *label, uint8_t *gt, void *workspace,
                       size_t workspace_bytes, hipStream_t s);
 
+// label maps as indexed PNG file images (png_encode.hip)
+size_t label_png_bound(int H, int W);
+size_t label_pngs_workspace_bytes(int F, int H, int W);
+int launch_label_pngs(const uint8_t *labels, int F, int H, int W, const uint8_t *palette,
+                      uint8_t *out, size_t cap, int32_t *lengths, void *workspace,
+                      size_t workspace_bytes, hipStream_t s);
+
 // nms_with_mask_iou over all frames of a step (mask_nms_frames.hip)
 size_t mask_iou_nms_frames_workspace_bytes(int F, int cap, int rows, int im_h, int im_w);
 int launch_mask_iou_nms_frames(const float *masks, int rows, int R, const float *dets,

@@ -1256,6 +1256,19 @@ def frame_label_maps(pipe: FramePipeline, out: dict, thresh: float = 0.25, gt_th
                           rows_fit="counts_host" in out)
 
 
+def frame_label_pngs(pipe: FramePipeline, out: dict, thresh: float = 0.25, gt_thresh=None,
+                     lut=None, palette=None, valid=None):
+    """frame_label_maps, then every frame's `label` as its DAVIS annotation file, an
+    8-bit indexed PNG encoded on the device (ops.label_pngs; palette [256,3] uint8 RGB,
+    default vis.davis_palette()): -> dict(label, gt, streams [F,cap] uint8, lengths [F]
+    int32), all on the device and without a host read; streams[f, :lengths[f]] is
+    frame f's file (vis.png_bytes, vis.write_pngs).  Refuses and accepts what
+    frame_label_maps does."""
+    label, gt = frame_label_maps(pipe, out, thresh, gt_thresh, lut, valid)
+    streams, lengths = ops.label_pngs(label, palette)
+    return {"label": label, "gt": gt, "streams": streams, "lengths": lengths}
+
+
 def check_flow_args(flow, raw_flow, F, frame_hw, blob_hw, device):
     """VOSPipeline.run's flow arguments: at most one of flow (blob resolution) and
     raw_flow (F x H x W x 2 fp32 at frame resolution, on `device`); raw_flow needs
@@ -1456,6 +1469,15 @@ class VOSPipeline(FramePipeline):
         if float(self.cfg.TEST.NMS_WITH_MASK_IOU) > 0:
             valid = self.finalize(out)["valid"]
         return frame_label_maps(self, out, thresh, gt_thresh, lut, valid)
+
+    def frame_label_pngs(self, out: dict, thresh: float = 0.25, gt_thresh=None, lut=None,
+                         palette=None):
+        """frame_label_pngs of the maps self.frame_label_maps gives: with
+        TEST.NMS_WITH_MASK_IOU > 0 the files show the rows the mask-IoU NMS kept."""
+        valid = None
+        if float(self.cfg.TEST.NMS_WITH_MASK_IOU) > 0:
+            valid = self.finalize(out)["valid"]
+        return frame_label_pngs(self, out, thresh, gt_thresh, lut, palette, valid)
 
     def backbone(self, frames):
         feats = super().backbone(frames)

@@ -2131,6 +2131,60 @@ def label_maps(masks: torch.Tensor, dets: torch.Tensor, classes: torch.Tensor,
 
 
 # --------------------------------------------------------------------------- #
+# label maps as indexed PNG file images                                        #
+# --------------------------------------------------------------------------- #
+def label_png_bound(im_h: int, im_w: int) -> int:
+    """vd_label_png_bound: the bytes no H x W label map's PNG can exceed, which is the
+    per-frame capacity label_pngs allocates.  ValueError for a size the kernel does
+    not serve (W in 1..4095, H in 1..16384).  Needs no device."""
+    n = int(lib().vd_label_png_bound(int(im_h), int(im_w)))
+    if n == 0:
+        raise ValueError("label_png_bound: %d x %d is outside 1..16384 x 1..4095"
+                         % (int(im_h), int(im_w)))
+    return n
+
+
+def label_pngs(labels: torch.Tensor, palette: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None):
+    """Every frame's label map as a complete 8-bit indexed PNG file image, encoded on
+    the device (vd_label_pngs): labels [F,H,W] uint8 on the device (label_maps' label
+    or gt), palette [256,3] uint8 RGB (default: vis.davis_palette()), out an optional
+    [F,cap] uint8 device buffer with cap >= label_png_bound(H, W).  -> (streams [F,cap]
+    uint8, lengths [F] int32), both on the device: streams[f, :lengths[f]] is the file.
+    No host read, so the call follows a run(sync=False) step and can be graph-captured
+    (give `palette` as a device tensor then).  vis.png_bytes / vis.write_pngs bring
+    the files to the host."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be an F x H x W tensor")
+    F, H, W = (int(v) for v in labels.shape)
+    cap = label_png_bound(H, W)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != F or \
+                out.shape[1] < cap:
+            raise ValueError("out must be F x cap uint8 with cap >= label_png_bound(%d, %d) = "
+                             "%d, got %s" % (H, W, cap, tuple(getattr(out, "shape", ()))))
+    lab = _need(labels, "labels", torch.uint8)
+    if palette is None:
+        from . import vis
+        palette = vis.davis_palette().to(lab.device)
+    if not isinstance(palette, torch.Tensor) or tuple(palette.shape) != (256, 3):
+        raise ValueError("palette must be a 256 x 3 uint8 tensor")
+    pal = _need(palette.to(lab.device), "palette", torch.uint8)
+    if out is None:
+        out = torch.empty((F, cap), dtype=torch.uint8, device=lab.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 device tensor")
+    lengths = torch.empty((F,), dtype=torch.int32, device=lab.device)
+    if F == 0:
+        return out, lengths
+    ws = _ws(lib().vd_label_pngs_workspace(F, H, W), lab.device)
+    check(lib().vd_label_pngs(lab.data_ptr(), F, H, W, pal.data_ptr(), out.data_ptr(),
+                              out.shape[1], lengths.data_ptr(), ws.data_ptr(), ws.numel(),
+                              _stream()), "vd_label_pngs")
+    return out, lengths
+
+
+# --------------------------------------------------------------------------- #
 # keypoint_results: heatmap decode                                             #
 # --------------------------------------------------------------------------- #
 KEYPOINT_MAX_HEATMAP = 64  # csrc/keypoints.hip kKpMaxM
