@@ -960,6 +960,71 @@ int vd_label_pngs(const uint8_t *labels, int F, int H, int W, const uint8_t *pal
                   size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The objects of a label map: what the reference's host loops over np.unique(gt) make
+ * of an H x W object-ID map, for every frame of a step in one call.
+ * DAVIS_imdb.get_gt / get_bboxes (imdb/vos/davis_db.py:180-204) with the box form of
+ * lib_vos/tools/get_cls_mapper.py:129-136 (the boxes the heads then run on through
+ * box_proposals), and DAVIS_imdb.add_gt_annotations_to_entry (davis_db.py:407-517,
+ * called from lib_vos/tools/train_davis_online.py:429 on the last_gt that
+ * viz_mask_result returned).
+ *
+ * vd_label_objects: labels F x H x W u8 (device; vd_label_maps' gt or label, or a
+ * DAVIS annotation).  Per frame, in this order:
+ *   values    the distinct values of the map.  remap255 == 1 applies get_gt's rule
+ *             first: if 255 occurs, its pixels take the value len(vals) - 1, vals
+ *             counting every distinct value of the raw map (0 and 255 included); if
+ *             that value occurs already the two objects merge, as in the reference.
+ *             The objects are the non-zero values in ascending order (np.unique).
+ *   ids       F x obj_cap u8        the object's value
+ *   rects     F x obj_cap x 4 i32   cv2.boundingRect (x, y, w, h) = (xmin, ymin,
+ *                                   xmax - xmin + 1, ymax - ymin + 1)
+ *   areas     F x obj_cap i32       the pixel count
+ *   boxes     F x obj_cap x 4 fp32, counts F i32: the box_proposals layout
+ *             vd_rois_from_boxes takes.
+ *             expand < 0, the "rect" form: (x, y, x + w, y + h); every object kept.
+ *             expand >= 0, the "entry" form (the reference uses 0.05), in float64:
+ *             e = sqrt(w * h) * expand (the correctly rounded square root); x -= e / 2,
+ *             y -= e / 2, w += e, h += e (_expand_box); x2 = x + max(0, w - 1), y2
+ *             likewise (xywh_to_xyxy); every coordinate clipped to [0, W - 1] /
+ *             [0, H - 1] (clip_xyxy_to_image); an object is kept iff area > 0 and
+ *             x2 > x1 and y2 > y1.  The kept rows are compacted in order, ids / rects /
+ *             areas / RLE rows with them; the store rounds to float32 once
+ *             (entry['boxes'] is float32).  Nothing is fused (-ffp-contract=off).
+ *   counts[f] the number of kept objects; 0 for a frame without one.  More than
+ *             obj_cap: counts[f] = VD_COUNT_SELECT_FAILED and nothing else is written
+ *             for that frame (vd_rois_from_boxes' convention).
+ *   rle_cap > 0: rle_counts F x obj_cap x rle_cap u32, rle_n F x obj_cap i32: the
+ *             pycocotools mask.encode counts of (map == value) after the remap,
+ *             column-major, the first run counting zeros; rle_n the number of runs.
+ *             An object with more than rle_cap runs gets rle_n = -n and no counts
+ *             (vd_mask_rle's retry contract).  rle_cap == 0: no RLE, both may be NULL.
+ * Rows past counts[f] are not written in any output.
+ *
+ * No host read, no device allocation, nothing sized by a device value: the call can
+ * be graph-captured.  The outputs depend on the inputs alone (the statistics are
+ * merged with integer min / max / add atomics, which commute), whatever the workspace
+ * held.  Workspace: vd_label_objects_workspace_size(F, H, W, obj_cap) =
+ * F * (5136 + 32 * obj_cap) bytes (a 256 x 5 int32 table, the slot count, one 32-byte
+ * slot per object), 16-byte aligned; 0 for a shape the kernels refuse (F == 0 included:
+ * there is nothing to carve).  The caller's rle_counts is F * obj_cap * rle_cap * 4 bytes
+ * -- at obj_cap 255 and rle_cap 4 W + 2 that is 348 MB for 64 maps of 800 x 1333, five
+ * times the maps: size obj_cap to the objects expected.  The RLE pass launches obj_cap x F
+ * workgroups, of which those past a frame's count return at once.
+ *
+ * 1 <= obj_cap <= 255, F <= 65535, H >= 1, 1 <= W <= 8192 (the RLE pass keeps one
+ * int per column in LDS), H * W < 2^31 (VD_ERR_SHAPE otherwise); a workspace below the
+ * size gives VD_ERR_WORKSPACE; NULL labels / ids / rects / areas / boxes / counts /
+ * workspace, NULL rle_counts / rle_n with rle_cap > 0, rle_cap < 0, remap255 outside
+ * {0, 1}, a NaN expand or F < 0 give VD_ERR_ARG.  Nothing is launched on an error.
+ * F == 0 returns VD_OK.
+ * ------------------------------------------------------------------------- */
+size_t vd_label_objects_workspace_size(int F, int H, int W, int obj_cap);
+int vd_label_objects(const uint8_t *labels, int F, int H, int W, int remap255, double expand,
+                     int obj_cap, int rle_cap, uint8_t *ids, int32_t *rects, int32_t *areas,
+                     float *boxes, int32_t *counts, uint32_t *rle_counts, int32_t *rle_n,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * nms_with_mask_iou (lib_vos/tools/vos_test.py:985-1029) for every frame of a
  * step in one call, without the H x W planes and without a host read.
  *

@@ -158,6 +158,10 @@ SIGNATURES = {
     "vd_label_maps_workspace_size": (_S, [_I, _I]),
     "vd_label_maps": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _I, _P, _P,
                            _P, _S, _P]),
+    # the objects of a label map (boxes, areas, RLE)
+    "vd_label_objects_workspace_size": (_S, [_I, _I, _I, _I]),
+    "vd_label_objects": (_I, [_P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _P, _P, _P, _P, _P,
+                              _P, _P, _P, _S, _P]),
     # label maps as indexed PNG file images
     "vd_label_png_bound": (_S, [_I, _I]),
     "vd_label_pngs_workspace": (_S, [_I, _I, _I]),

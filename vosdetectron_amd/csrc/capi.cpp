@@ -770,6 +770,24 @@ int vd_label_pngs(const uint8_t *labels, int F, int H, int W, const uint8_t *pal
                              workspace_bytes, VD_STREAM(stream));
 }
 
+size_t vd_label_objects_workspace_size(int F, int H, int W, int obj_cap) {
+    return label_objects_workspace_bytes(F, H, W, obj_cap);
+}
+
+int vd_label_objects(const uint8_t *labels, int F, int H, int W, int remap255, double expand,
+                     int obj_cap, int rle_cap, uint8_t *ids, int32_t *rects, int32_t *areas,
+                     float *boxes, int32_t *counts, uint32_t *rle_counts, int32_t *rle_n,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    if (F == 0) return VD_OK;
+    if (!labels || !ids || !rects || !areas || !boxes || !counts || F < 0 || rle_cap < 0 ||
+        (rle_cap > 0 && (!rle_counts || !rle_n)) || (remap255 != 0 && remap255 != 1) ||
+        expand != expand)
+        return VD_ERR_ARG;
+    return launch_label_objects(labels, F, H, W, remap255, expand, obj_cap, rle_cap, ids, rects,
+                                areas, boxes, counts, rle_counts, rle_n, workspace,
+                                workspace_bytes, VD_STREAM(stream));
+}
+
 size_t vd_mask_iou_nms_frames_workspace_size(int F, int cap, int rows, int im_h, int im_w) {
     return mask_iou_nms_frames_workspace_bytes(F, cap, rows, im_h, im_w);
 }

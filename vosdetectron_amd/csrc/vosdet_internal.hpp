@@ -242,6 +242,13 @@ int launch_label_maps(const float *masks, int R, const float *dets, const int32_
                       const uint8_t *lut, int lut_n, uint8_t *label, uint8_t *gt, void *workspace,
                       size_t workspace_bytes, hipStream_t s);
 
+// the objects of a label map: ids, rects, areas, boxes, RLE (label_objects.hip)
+size_t label_objects_workspace_bytes(int F, int H, int W, int obj_cap);
+int launch_label_objects(const uint8_t *labels, int F, int H, int W, int remap255, double expand,
+                         int obj_cap, int rle_cap, uint8_t *ids, int32_t *rects, int32_t *areas,
+                         float *boxes, int32_t *counts, uint32_t *rle_counts, int32_t *rle_n,
+                         void *workspace, size_t workspace_bytes, hipStream_t s);
+
 // label maps as indexed PNG file images (png_encode.hip)
 size_t label_png_bound(int H, int W);
 size_t label_pngs_workspace_bytes(int F, int H, int W);

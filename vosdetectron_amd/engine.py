@@ -1269,6 +1269,24 @@ def frame_label_pngs(pipe: FramePipeline, out: dict, thresh: float = 0.25, gt_th
     return {"label": label, "gt": gt, "streams": streams, "lengths": lengths}
 
 
+def frame_label_objects(pipe: FramePipeline, out: dict, thresh: float = 0.25, gt_thresh=None,
+                        lut=None, valid=None, which: str = "gt", **kw):
+    """frame_label_maps, then the objects of every frame's `gt` (or `label`) map
+    (ops.label_objects; kw: expand, remap255, obj_cap, rle_cap, want_rle, out): the
+    reference's add_gt_annotations_to_entry on the last_gt viz_mask_result returned
+    (train_davis_online.py:429), or with expand=None get_bboxes' boxes.  -> the
+    ops.label_objects dict plus label and gt, all on the device; (boxes, counts) is a
+    box_proposals argument of run().  Refuses and accepts what frame_label_maps does."""
+    if which not in ("gt", "label"):
+        raise ValueError("which must be 'gt' or 'label', got %r" % (which,))
+    if which == "gt" and gt_thresh is None:
+        raise ValueError("frame_label_objects: which='gt' needs gt_thresh")
+    label, gt = frame_label_maps(pipe, out, thresh, gt_thresh, lut, valid)
+    res = dict(ops.label_objects(gt if which == "gt" else label, **kw))
+    res["label"], res["gt"] = label, gt
+    return res
+
+
 def check_flow_args(flow, raw_flow, F, frame_hw, blob_hw, device):
     """VOSPipeline.run's flow arguments: at most one of flow (blob resolution) and
     raw_flow (F x H x W x 2 fp32 at frame resolution, on `device`); raw_flow needs
@@ -1478,6 +1496,15 @@ class VOSPipeline(FramePipeline):
         if float(self.cfg.TEST.NMS_WITH_MASK_IOU) > 0:
             valid = self.finalize(out)["valid"]
         return frame_label_pngs(self, out, thresh, gt_thresh, lut, palette, valid)
+
+    def frame_label_objects(self, out: dict, thresh: float = 0.25, gt_thresh=None, lut=None,
+                            which: str = "gt", **kw):
+        """frame_label_objects of the maps self.frame_label_maps gives: with
+        TEST.NMS_WITH_MASK_IOU > 0 the objects of the rows the mask-IoU NMS kept."""
+        valid = None
+        if float(self.cfg.TEST.NMS_WITH_MASK_IOU) > 0:
+            valid = self.finalize(out)["valid"]
+        return frame_label_objects(self, out, thresh, gt_thresh, lut, valid, which, **kw)
 
     def backbone(self, frames):
         feats = super().backbone(frames)

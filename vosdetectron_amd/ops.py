@@ -2185,6 +2185,118 @@ def label_pngs(labels: torch.Tensor, palette: Optional[torch.Tensor] = None,
 
 
 # --------------------------------------------------------------------------- #
+# the objects of a label map: boxes, areas, RLE                                #
+# --------------------------------------------------------------------------- #
+LABEL_OBJECTS_MAX_CAP = 255    # csrc/label_objects.hip kObjMaxCap
+LABEL_OBJECTS_MAX_WIDTH = 8192  # kObjMaxW
+
+_LABEL_OBJECT_FIELDS = (("ids", torch.uint8, ()), ("rects", torch.int32, (4,)),
+                        ("areas", torch.int32, ()), ("boxes", torch.float32, (4,)))
+
+
+def label_objects(labels: torch.Tensor, expand: Optional[float] = 0.05, remap255: bool = False,
+                  obj_cap: int = 255, rle_cap: Optional[int] = None, want_rle: bool = True,
+                  out: Optional[dict] = None) -> dict:
+    """The objects of every frame's label map in one call (vd_label_objects): labels
+    [F,H,W] uint8 on the device (label_maps' gt or label, or DAVIS annotations).  Per
+    distinct non-zero value, ascending: ids [F,obj_cap] uint8, rects [F,obj_cap,4] int32
+    (cv2.boundingRect), areas [F,obj_cap] int32, boxes [F,obj_cap,4] fp32 and counts [F]
+    int32 -- (boxes, counts) is what FramePipeline.run takes as box_proposals --, and with
+    want_rle rle_counts [F,obj_cap,rle_cap] int32 / rle_n [F,obj_cap] int32, the
+    pycocotools mask.encode counts of (map == value) (rle_strings gives the strings);
+    both None without want_rle.  expand=None: boxes (x, y, x + w, y + h) of get_bboxes /
+    get_cls_mapper, every object kept; expand >= 0: add_gt_annotations_to_entry's
+    expanded, clipped boxes in float64 and its validity filter (rows compacted).
+    remap255: get_gt's rule for value 255 first.  A frame with more than obj_cap kept
+    objects has counts[f] = -1 (raise_on_failed_counts).  Rows past a count are not
+    written.
+    Without `out` and `rle_cap` the call retries with a larger rle_cap when an object has
+    more runs (one host read; first try 4 * W + 2).  With `out` (a dict of the output
+    tensors, as a previous call returned them; reused, so the call can be captured) or an
+    explicit rle_cap there is no host read: an object with more than rle_cap runs has
+    rle_n = -n and no counts.
+    Device footprint: rle_counts is F * obj_cap * rle_cap * 4 bytes -- 348 MB for 64 maps
+    of 800 x 1333 at the defaults (obj_cap 255, rle_cap 4 * W + 2), five times the maps;
+    only the rows below the counts are ever copied to the host.  Give the obj_cap the maps
+    need (DAVIS: <= 10 objects; davis_db uses 32), and want_rle=False where only boxes are
+    wanted: the RLE pass launches obj_cap x F workgroups, those past a count return at
+    once."""
+    lab = _need(labels, "labels", torch.uint8)
+    if lab.dim() != 3:
+        raise ValueError("labels must be F x H x W, got %s" % (tuple(lab.shape),))
+    F, H, W = (int(v) for v in lab.shape)
+    obj_cap = int(obj_cap)
+    if not 1 <= obj_cap <= LABEL_OBJECTS_MAX_CAP:
+        raise ValueError("label_objects: obj_cap = %d is outside 1..%d"
+                         % (obj_cap, LABEL_OBJECTS_MAX_CAP))
+    if H < 1 or W < 1 or W > LABEL_OBJECTS_MAX_WIDTH or H * W >= 2 ** 31 or F > 65535:
+        raise ValueError("label_objects: %d maps of %d x %d are outside 1..65535 maps, width "
+                         "1..%d, H * W < 2^31" % (F, H, W, LABEL_OBJECTS_MAX_WIDTH))
+    if expand is not None and not float(expand) >= 0.0:
+        raise ValueError("label_objects: expand = %r is neither None nor >= 0" % (expand,))
+    ex = -1.0 if expand is None else float(expand)
+    retry = out is None and rle_cap is None and want_rle
+    dev = lab.device
+    if out is not None:
+        for name, dt, tail in _LABEL_OBJECT_FIELDS + (("counts", torch.int32, None),):
+            t = out.get(name)
+            want = (F,) if tail is None else (F, obj_cap) + tail
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+                raise ValueError("out[%r] must be %s" % (name, want))
+            _need(t, "out[%r]" % name, dt)
+        if want_rle:
+            rc, rn = out.get("rle_counts"), out.get("rle_n")
+            if not isinstance(rc, torch.Tensor) or rc.dim() != 3 or \
+                    tuple(rc.shape[:2]) != (F, obj_cap) or rc.shape[2] < 1 or \
+                    not isinstance(rn, torch.Tensor) or tuple(rn.shape) != (F, obj_cap):
+                raise ValueError("out['rle_counts'] must be F x obj_cap x rle_cap and "
+                                 "out['rle_n'] F x obj_cap")
+            _need(rc, "out['rle_counts']", torch.int32)
+            _need(rn, "out['rle_n']", torch.int32)
+            if rle_cap is not None and int(rle_cap) != rc.shape[2]:
+                raise ValueError("rle_cap = %d but out['rle_counts'] holds %d per object"
+                                 % (int(rle_cap), rc.shape[2]))
+            rle_cap = int(rc.shape[2])
+        res = dict(out)
+    else:
+        res = {name: torch.empty((F, obj_cap) + tail, dtype=dt, device=dev)
+               for name, dt, tail in _LABEL_OBJECT_FIELDS}
+        res["counts"] = torch.empty((F,), dtype=torch.int32, device=dev)
+    if not want_rle:
+        res["rle_counts"] = res["rle_n"] = None
+        cap = 0
+    else:
+        cap = int(rle_cap) if rle_cap is not None else 4 * W + 2
+        if cap < 1:
+            raise ValueError("label_objects: rle_cap = %d must be positive" % cap)
+    if F == 0:
+        if want_rle and out is None:
+            res["rle_counts"] = torch.empty((0, obj_cap, cap), dtype=torch.int32, device=dev)
+            res["rle_n"] = torch.empty((0, obj_cap), dtype=torch.int32, device=dev)
+        return res
+    ws = _ws(lib().vd_label_objects_workspace_size(F, H, W, obj_cap), dev)
+    while True:
+        if want_rle and out is None:
+            res["rle_counts"] = torch.empty((F, obj_cap, cap), dtype=torch.int32, device=dev)
+            res["rle_n"] = torch.empty((F, obj_cap), dtype=torch.int32, device=dev)
+        check(lib().vd_label_objects(
+            lab.data_ptr(), F, H, W, 1 if remap255 else 0, ex, obj_cap, cap,
+            res["ids"].data_ptr(), res["rects"].data_ptr(), res["areas"].data_ptr(),
+            res["boxes"].data_ptr(), res["counts"].data_ptr(),
+            res["rle_counts"].data_ptr() if want_rle else None,
+            res["rle_n"].data_ptr() if want_rle else None, ws.data_ptr(), ws.numel(),
+            _stream()), "vd_label_objects")
+        if not retry:
+            return res
+        # rows past a count hold no defined value: look at the written rows only
+        live = torch.arange(obj_cap, device=dev)[None, :] < res["counts"][:, None]
+        need = int(torch.where(live, -res["rle_n"], 0).max().item())
+        if need <= cap:
+            return res
+        cap = need
+
+
+# --------------------------------------------------------------------------- #
 # keypoint_results: heatmap decode                                             #
 # --------------------------------------------------------------------------- #
 KEYPOINT_MAX_HEATMAP = 64  # csrc/keypoints.hip kKpMaxM
